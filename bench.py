@@ -15,8 +15,15 @@ cluster.TrmvShardExchange, the code path the tests check).  --weak instead
 gives every rank its own 2^20 keys and 100M ops (per-GPU work fixed); at N > 1
 the line's detail carries a short weak leg too.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`
+and `ms_per_step`, with the HIP-event kernel times the timed steps recorded.
+--dump-outputs DIR also writes what the last timed step left (dump_outputs).
+--full adds every other leg, each after the timed steps and never in `value`:
+the tier-0 roofline's byte accounting, the host entry, the steady-state leg,
+the CPU baselines and (N > 1) the weak-scaling leg.
 
 Prints ONE JSON line on rank 0.
 """
@@ -39,6 +46,13 @@ def parse():
     # (the driver's command: 20 timed steps of ~2.2 ms after 5 warmup steps)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(rank 0's shard at N > 1; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: roofline byte accounting, host entry, "
+                         "steady state, CPU baselines, (N > 1) weak scaling; the options that size "
+                         "those legs have no effect without it")
     ap.add_argument("--n-ops", type=int, default=100_000_000)
     ap.add_argument("--n-keys", type=int, default=1 << 20)
     ap.add_argument("--k", type=int, default=100)
@@ -100,6 +114,103 @@ def cpu_model():
     except OSError:
         pass
     return platform.processor() or "unknown"
+
+
+DUMP_BUDGET = 60_000_000  # bytes of .npy data per dump (under the 64 MB a comparison may read)
+DUMP_RANGES, DUMP_RANGE_KEYS = 16, 256
+DUMP_KEY_SIZE_KEYS = 1 << 20
+DUMP_EXTRA_ROWS = 1 << 16
+
+
+def dump_outputs(out_dir, eng, xres=None):
+    """What the last timed step left, as out_dir/<name>.npy: the state a caller
+    of reset + apply_device reads back, and the extra effects it ships.
+
+    key_sizes [4, m] float32: players, masked, removal rows, observed of every
+      key (of key_sizes_keys when there are more than 2^20: a seeded sample);
+    state_*: the canonical image (TrmvState) of up to 16 seeded ranges of 256
+      keys (state_keys), every element of it: offsets as per-key counts
+      (state_*_count), DcIds, counts and flags float32, the int64 columns
+      (Ids, scores, clocks) float64, exact below 2^53;
+    extras [n, 6 + n_dc] float64: the extra effects (op, kind, id, score, dc,
+      ts, vc...) in stream order, the first 2^16 of them; extra_count [1];
+    replica_vc [n_dc] float64: the elementwise max of the keys' Vc;
+    exchange_rows / exchange_vc (N > 1): what the step's exchange returned.
+    The sample depends only on the engine's key count; ranges that would take
+    the dump past DUMP_BUDGET bytes are left out."""
+    import numpy as np
+
+    from antidote_ccrdt_amd import _lib
+    from antidote_ccrdt_amd.engine import DeviceArray
+    os.makedirs(out_dir, exist_ok=True)
+    left = [DUMP_BUDGET]
+
+    def put(name, a, dtype):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.nbytes > left[0]:
+            raise RuntimeError(f"--dump-outputs: {name} would take the dump past {DUMP_BUDGET} bytes")
+        left[0] -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    eng.sync()
+    n_keys, D = eng.n_keys, eng.n_dc
+    rng = np.random.default_rng(0xD0C5)
+    # extras and replica Vc, through the device entry points the exchange uses
+    n_extra = eng.extra_count()
+    cap = max(1, n_extra)  # all of them: which rows a smaller buffer would keep is not fixed
+    d_rows = DeviceArray(np.zeros((cap, 6 + D), np.int64))
+    d_cnt = DeviceArray(np.zeros(1, np.uint32))
+    d_vc = DeviceArray(np.zeros(D, np.int64))
+    eng.extras_device(d_rows.p, cap, d_cnt.p)
+    eng.replica_vc_device(d_vc.p)
+    eng.sync()
+    h_rows, h_vc = np.zeros((cap, 6 + D), np.int64), np.zeros(D, np.int64)
+    for h, d in ((h_rows, d_rows), (h_vc, d_vc)):
+        _lib.check(_lib.lib.ccrdt_memcpy_d2h(_lib.ptr(h), d.p, h.nbytes), "d2h")
+        d.close()
+    d_cnt.close()
+    h_rows = h_rows[:n_extra]
+    h_rows[h_rows[:, 1] == 2, 3:6] = 0  # {rmv, {Id, Vc}} carries no score, DcId or Ts
+    put("extras", h_rows[np.argsort(h_rows[:, 0], kind="stable")][:DUMP_EXTRA_ROWS], np.float64)
+    put("extra_count", [n_extra], np.float64)
+    put("replica_vc", h_vc, np.float64)
+    if xres:
+        x_rows = xres["rows"].cpu().numpy().copy()  # (sorted by global op)
+        x_rows[x_rows[:, 1] == 2, 3:6] = 0
+        put("exchange_rows", x_rows[:DUMP_EXTRA_ROWS], np.float64)
+        put("exchange_vc", xres["vc"].cpu().numpy(), np.float64)
+    # per-key sizes of the whole state
+    ks = eng.key_sizes()
+    sizes = np.stack([ks[c] for c in ("np", "nm", "nr", "nobs")])
+    if n_keys > DUMP_KEY_SIZE_KEYS:
+        keys = np.sort(rng.choice(n_keys, DUMP_KEY_SIZE_KEYS, replace=False))
+        put("key_sizes_keys", keys, np.float64)
+        sizes = sizes[:, keys]
+    put("key_sizes", sizes, np.float32)
+    # the canonical image of the sampled key ranges
+    w = min(DUMP_RANGE_KEYS, n_keys)
+    if n_keys <= DUMP_RANGES * w:
+        starts, w = [0], n_keys
+    else:
+        starts = sorted(int(x) * w for x in rng.choice(n_keys // w, DUMP_RANGES, replace=False))
+    f32 = {"obs_dc", "m_dc", "min_dc", "min_valid", "obs_count", "m_count", "r_count"}
+    cols = {}
+    room = left[0]
+    for k0 in starts:
+        st = eng.export_range(k0, k0 + w)
+        part = {"keys": np.arange(k0, k0 + w)}
+        for name, a in vars(st).items():
+            if name.endswith("_ptr"):
+                name, a = name[:-4] + "_count", np.diff(a.astype(np.int64))
+            part[name] = a
+        need = sum(int(a.size) * (4 if name in f32 else 8) for name, a in part.items())
+        if need > room:
+            break
+        room -= need
+        for name, a in part.items():
+            cols.setdefault(name, []).append(a)
+    for name, parts in cols.items():
+        put("state_" + name, np.concatenate(parts), np.float32 if name in f32 else np.float64)
 
 
 def main():
@@ -190,12 +301,87 @@ def main():
     ms_per_step = dt * 1000.0 / args.steps
     value = (1 if sharded else world) * args.n_ops * args.steps / dt
 
+    # what the timed steps themselves recorded (HIP events on the engine
+    # stream, host counters): no further GPU work
+    chain_ms = sum(kms) / len(kms)
+    t0_ms = sum(t0s) / len(t0s)  # tier 0's HIP-event interval, mean over the timed steps
+    # 0 = tier 0, 1 / 2 = tier S (up to 256 / 1024 players per key), 3 = tier R
+    # (resident keys; the first tier of a batch onto resident state), 4 = the
+    # HBM class of tier S (keys past 1024 players)
+    tiers = (0, 1, 2, 3, 4)
+    overflow = {c: eng.overflow_keys(c) for c in tiers}
+    tier_ms = {c: round(eng.tier_ms(c), 4) for c in tiers}
+    exchange = (None if shard is None else
+                {"backend": backend, "extras_all_gathered": int(xres["rows"].shape[0]),
+                 "ms_per_step": sum(xms) / max(1, len(xms)),
+                 "replica_vc": [int(v) for v in xres["vc"].cpu().tolist()],
+                 "in_step": "cluster.TrmvShardExchange: the rank's pack [word | Vc | rows] "
+                            "written by ccrdt_trmv_exchange_pack (no host wait), one all_gather "
+                            "of [word | Vc | first 256 effect rows] into a [world, L] tensor, "
+                            "ccrdt_trmv_exchange_reduce (counts, flags, Vc max, rows sorted by "
+                            "global op), one host read of the header; a second gather only past "
+                            "256 rows",
+                 "ms_per_step_what": "wall time of TrmvShardExchange.run (includes waiting for the "
+                                     "pack kernels queued after the apply)"})
+    head = {
+        "metric": "CRDT ops/sec (topk_rmv, 1M keys, 8-DC vclocks)",
+        "value": value,
+        "unit": "ops/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        # N = 1 runs the strong series' fixed configs[2] workload (--weak
+        # only changes what N > 1 does)
+        "scaling": "weak" if args.weak else "strong",
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"antidote_ccrdt_topk_rmv update/2, K={args.k}, {args.n_dc}-DC "
+                        f"vector clocks, {args.n_ops} effect ops (90% add / 10% rmv, 256 "
+                        f"players/key, score U[1,1e6], rmv lag U[0,64)) CSR-grouped over "
+                        f"{args.n_keys} fresh keys"
+                        + (", one global keyspace hash-sharded over the GPUs" if sharded else
+                           " per GPU") + ", ops resident in HBM",
+            "n_ops_total": args.n_ops * (1 if sharded else world),
+            "n_keys_total": args.n_keys * (1 if sharded else world),
+            "n_keys_rank0": n_local_keys, "n_ops_rank0": int(b.n_ops), "K": args.k,
+            "n_dc": args.n_dc,
+            "parallelism": (f"key-sharded x{world} (splitmix64(key) mod {world})" if sharded else
+                            f"independent shards x{world}")
+                           + (f", {backend} exchange per step" if world > 1 else ""),
+            "seed": "0xCC0DE+2" + ("" if (sharded or world == 1) else " (+1000003*rank)"),
+        },
+    }
+
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, eng, xres)
+        barrier()
+
+    if not args.full:
+        # the plain run ends here: the headline and what its steps recorded
+        if rank == 0:
+            print(json.dumps({**head, "roofline": None, "cpu_baseline": None, "detail": {
+                "full": False,
+                "apply_chain": {"kernel_ms": chain_ms},
+                "tier0_kernel_ms": t0_ms,
+                "tier0_kernel_ms_steps": [round(x, 4) for x in t0s],
+                "keys_handed_on_by_tier": overflow,
+                "kernel_ms_by_tier": tier_ms,
+                "gen_s": round(t_gen, 2),
+                "exchange": exchange}}), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     # Dominant kernel: tier 0 of the apply chain (trmv_wave_kernel), which
     # completes every key except the few it hands on.  Its algorithmic bytes
     # are counted exactly per key (ops in + final state out) over the keys it
     # completed; its time is HIP events around its launch on the engine stream.
     import numpy as np
-    chain_ms = sum(kms) / len(kms)
     sizes = eng.sizes()
     n_extra = eng.extra_count()
     ks = eng.key_sizes()
@@ -212,7 +398,6 @@ def main():
     tier0[handed] = False
     alg_bytes = int(key_bytes.sum()) + 32 * n_extra          # whole batch
     alg_bytes_t0 = int(key_bytes[tier0].sum()) + 32 * n_extra  # extras: 46 per 100M ops, all counted here
-    t0_ms = sum(t0s) / len(t0s)  # tier 0's HIP-event interval, mean over the timed steps
     kernel_ms = t0_ms
     achieved = alg_bytes_t0 / (t0_ms * 1e-3) / 1e9
     traffic = steady_traffic = None
@@ -225,13 +410,6 @@ def main():
                 steady_traffic = (pm.get("steady") or {}).get("hbm_bytes_per_launch")
         except (OSError, ValueError):
             traffic = steady_traffic = None
-    # 0 = tier 0, 1 / 2 = tier S (up to 256 / 1024 players per key), 3 = tier R
-    # (resident keys; the first tier of a batch onto resident state), 4 = the
-    # HBM class of tier S (keys past 1024 players)
-    tiers = (0, 1, 2, 3, 4)
-
-    overflow = {c: eng.overflow_keys(c) for c in tiers}
-    tier_ms = {c: round(eng.tier_ms(c), 4) for c in tiers}
 
     # Host entry (reported in detail, never `value`): ccrdt_trmv_apply from
     # host arrays -- the batch crosses PCIe to the device, the extras come back.
@@ -504,36 +682,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "CRDT ops/sec (topk_rmv, 1M keys, 8-DC vclocks)",
-            "value": value,
-            "unit": "ops/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            # N = 1 runs the strong series' fixed configs[2] workload (--weak
-            # only changes what N > 1 does)
-            "scaling": "weak" if args.weak else "strong",
-            "vs_baseline": None,
-            "dtype": "int64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"antidote_ccrdt_topk_rmv update/2, K={args.k}, {args.n_dc}-DC "
-                            f"vector clocks, {args.n_ops} effect ops (90% add / 10% rmv, 256 "
-                            f"players/key, score U[1,1e6], rmv lag U[0,64)) CSR-grouped over "
-                            f"{args.n_keys} fresh keys"
-                            + (", one global keyspace hash-sharded over the GPUs" if sharded else
-                               " per GPU") + ", ops resident in HBM",
-                "n_ops_total": args.n_ops * (1 if sharded else world),
-                "n_keys_total": args.n_keys * (1 if sharded else world),
-                "n_keys_rank0": n_local_keys, "n_ops_rank0": int(b.n_ops), "K": args.k,
-                "n_dc": args.n_dc,
-                "parallelism": (f"key-sharded x{world} (splitmix64(key) mod {world})" if sharded else
-                                f"independent shards x{world}")
-                               + (f", {backend} exchange per step" if world > 1 else ""),
-                "seed": "0xCC0DE+2" + ("" if (sharded or world == 1) else " (+1000003*rank)"),
-            },
+            **head,
             "roofline": {
                 "bound": "hbm",
                 "kernel": "trmv_wave_kernel<true, 5> (tier 0)",
@@ -562,18 +711,7 @@ def main():
                 "kernel_ms_by_tier": tier_ms,
                 "gen_s": round(t_gen, 2),
                 "weak_scaling": weak,
-                "exchange": (None if shard is None else
-                             {"backend": backend, "extras_all_gathered": int(xres["rows"].shape[0]),
-                              "ms_per_step": sum(xms) / max(1, len(xms)),
-                              "replica_vc": [int(v) for v in xres["vc"].cpu().tolist()],
-                              "in_step": "cluster.TrmvShardExchange: the rank's pack [word | Vc | rows] "
-                                         "written by ccrdt_trmv_exchange_pack (no host wait), one all_gather "
-                                         "of [word | Vc | first 256 effect rows] into a [world, L] tensor, "
-                                         "ccrdt_trmv_exchange_reduce (counts, flags, Vc max, rows sorted by "
-                                         "global op), one host read of the header; a second gather only past "
-                                         "256 rows",
-                              "ms_per_step_what": "wall time of TrmvShardExchange.run (includes waiting for the "
-                                                  "pack kernels queued after the apply)"}),
+                "exchange": exchange,
             },
         }
         print(json.dumps(out), flush=True)

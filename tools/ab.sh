@@ -7,7 +7,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 one() {  # name lib
-  timeout -k 10 300 env CCRDT_LIB="$PWD/$2" python bench.py --steps 10 --warmup 3 --cpu-sample-keys 0 \
+  timeout -k 10 300 env CCRDT_LIB="$PWD/$2" python bench.py --full --steps 10 --warmup 3 --cpu-sample-keys 0 \
     --cpu-steady-keys 0 --steady-batches "${STEADY:-0}" > "gpurun_out/ab_$1.log" 2>&1
   local rc=$?
   [ $rc -eq 0 ] || { tail -5 "gpurun_out/ab_$1.log"; exit $rc; }

@@ -3,8 +3,8 @@
 # as name=ENV=VAL[,ENV=VAL...] arguments, each run twice (A B A B order).
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
-B="--steps 20 --warmup 5 --cpu-sample-keys 0 --cpu-steady-keys 0 --steady-batches 0"
-E="--n-keys 131072 --n-ops 12500000 --steps 50 --warmup 10 --cpu-sample-keys 0 --cpu-steady-keys 0 --steady-batches 0"
+B="--full --steps 20 --warmup 5 --cpu-sample-keys 0 --cpu-steady-keys 0 --steady-batches 0"
+E="--full --n-keys 131072 --n-ops 12500000 --steps 50 --warmup 10 --cpu-sample-keys 0 --cpu-steady-keys 0 --steady-batches 0"
 for r in 1 2; do
 for spec in "$@"; do
   name=${spec%%=*}; envs=${spec#*=}; envs=${envs//,/ }

@@ -15,9 +15,9 @@ step() {  # name, timeout, command...
 }
 [ -z "$SKIP_TESTS" ] && step pytest_gpu 1500 python -u -m pytest ${TESTS:-tests} -m gpu -x -v --timeout 900 --timeout-method thread
 [ -z "$SKIP_TESTS" ] && step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-[ -z "$SKIP_BENCH" ] && step bench 600 python bench.py
+[ -z "$SKIP_BENCH" ] && step bench 600 python bench.py --full
 # EIGHTH=1: what one rank of the N=8 strong line does, on one GPU (1/8 of the keys and ops)
-[ -n "$EIGHTH" ] && step bench_eighth 300 python bench.py --n-keys 131072 --n-ops 12500000 --steps 50 --warmup 10 \
+[ -n "$EIGHTH" ] && step bench_eighth 300 python bench.py --full --n-keys 131072 --n-ops 12500000 --steps 50 --warmup 10 \
   --cpu-sample-keys 0 --cpu-steady-keys 0 --steady-batches 0
 if [ -z "$SKIP_PROF" ]; then
   echo "== kernel trace of the driver's bench command"
@@ -26,5 +26,5 @@ if [ -z "$SKIP_PROF" ]; then
       > "$GRAFT_REPO_ROOT/gpurun_out/kt_bench.log" 2>&1 ) || { tail -5 gpurun_out/kt_bench.log; exit 1; }
   python3 tools/kt_compare.py gpurun_out/kt gpurun_out/kt_bench.log | tee gpurun_out/kt_compare.txt
 fi
-[ -z "$SKIP_N2" ] && step bench_n2 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 3 --dist-backend gloo --steady-batches 1 --cpu-steady-keys 0
+[ -z "$SKIP_N2" ] && step bench_n2 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 10 --warmup 3 --dist-backend gloo --steady-batches 1 --cpu-steady-keys 0
 exit 0

@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc
 mkdir -p "$OUT"
-B="--steps 3 --warmup 1 --cpu-sample-keys 0 --cpu-steady-keys 0 --steady-batches ${STEADY:-4}"
+B="--full --steps 3 --warmup 1 --cpu-sample-keys 0 --cpu-steady-keys 0 --steady-batches ${STEADY:-4}"
 for pass in "write:WRITE_SIZE" "fetch:FETCH_SIZE" \
   "sq2:SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE" \
   "sq1:SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES"; do
