@@ -137,6 +137,9 @@ SIGNATURES = {
     "ccrdt_trmv_set_fresh_room": (INT, [P, INT]),
     "ccrdt_trmv_replica_vc_device": (INT, [P, P]),
     "ccrdt_trmv_extras_device": (INT, [P, P, I64, P]),
+    "ccrdt_trmv_value_size": (INT, [P, I64, P, C.POINTER(I64)]),
+    "ccrdt_trmv_value": (INT, [P, I64, P, P, P, P]),
+    "ccrdt_trmv_value_device": (INT, [P, I64, P, P, P, P, I64]),
     "ccrdt_trmv_exchange_pack": (INT, [P, P, I64, P, I64, C.c_uint32]),
     "ccrdt_trmv_exchange_reduce": (INT, [P, P, INT, I64, P, P]),
     "ccrdt_trmv_export": (INT, [P, C.POINTER(TrmvState)]),
@@ -175,6 +178,9 @@ SIGNATURES = {
     "ccrdt_wc_last_checks": (INT, [P, C.POINTER(I64)]),
     "ccrdt_wc_export": (INT, [P, P, P, P, P]),
     "ccrdt_lb_extras_device": (INT, [P, P, I64, P]),
+    "ccrdt_lb_value_size": (INT, [P, I64, P, C.POINTER(I64)]),
+    "ccrdt_lb_value": (INT, [P, I64, P, P, P, P]),
+    "ccrdt_lb_value_device": (INT, [P, I64, P, P, P, P, I64]),
     "ccrdt_wc_partition_device": (INT, [P, INT, P, P, I64, I64, P, P]),
     "ccrdt_wc_merge_device": (INT, [P, I64, P, P, I64]),
     "ccrdt_topk_range_size": (INT, [P, I64, I64, C.POINTER(I64)]),

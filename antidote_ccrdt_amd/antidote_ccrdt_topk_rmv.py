@@ -77,7 +77,8 @@ def value(state: TopkRmv):
     pairs in DESCENDING Id order; a larger map iterates in the BEAM's HAMT
     hash order (Q7), which this keeps as descending Id order too (compare
     larger lists as sets)."""
-    obs = sorted(((i, sc) for i, sc, _, _ in state._export()["obs"]), key=lambda p: terms.term_key(p[0]))
+    _, ids, scores = state.engine.values([0])
+    obs = sorted(zip(ids.tolist(), scores.tolist()), key=lambda p: terms.term_key(p[0]))
     return obs[::-1]
 
 

@@ -309,7 +309,8 @@ class leaderboard:
     @staticmethod
     def value(st: Leaderboard):
         """value/1 (:84-86): maps:to_list(Observed) (canonical: by Id, Q7)."""
-        return [tuple(x) for x in st.key_state()["obs"]]
+        _, ids, scores = st.engine.values([0])
+        return sorted(zip(ids.tolist(), scores.tolist()))
 
     @staticmethod
     def downstream(op, st: Leaderboard):

@@ -523,6 +523,22 @@ class ShardedTopkRmv:
     def export(self):
         return self.engine.export()
 
+    def value(self, global_keys):
+        """value/1 of keys of the global keyspace this rank owns, read on the
+        device (TopkRmvEngine.values): (ptr, id, score), segment i = Observed
+        of global_keys[i] ranked by cmp/2.  Raises KeyError for a key another
+        rank owns or a host-path key (its state is not in the engine)."""
+        g = np.asarray(global_keys, np.int64).reshape(-1)
+        own = np.asarray(self.keys, np.int64)
+        local = np.minimum(np.searchsorted(own, g), max(own.shape[0] - 1, 0))  # (own is ascending)
+        ok = own[local] == g if own.shape[0] else np.zeros(g.shape[0], bool)
+        if not ok.all():
+            raise KeyError(f"keys not owned by rank {self.rank}: {g[~ok][:8].tolist()}")
+        host = [int(k) for k in g.tolist() if k in self.host_keys]
+        if host:
+            raise KeyError(f"host-path keys (over the engine's per-key capacity): {host[:8]}")
+        return self.engine.values(local.astype(np.uint64))
+
 
 def _as_dict(x):
     if isinstance(x, dict):

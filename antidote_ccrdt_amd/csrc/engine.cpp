@@ -126,7 +126,8 @@ void ccrdt_engine::release_all() {
   for (DevBuf& d : st_nbase) d.release();
   for (DevBuf* d : {&arena, &obs_ord, &key_done, &partials, &ex_cnt, &ex, &ex_vc, &ex_key_ptr, &status, &op_pl,
                     &first_list, &ovl,
-                    &hbm_scratch, &st_kp,
+                    &hbm_scratch, &val_cnt, &val_caps, &val_part, &val_list, &val_keys, &val_ptr, &val_id,
+                    &val_score, &st_kp,
                     &st_kind, &st_id, &st_score, &st_dc, &st_ts, &st_rvc, &st_out_kind, &st_out_vc})
     d->release();
   release_types();

@@ -94,6 +94,10 @@ struct ccrdt_engine {
   hipEvent_t ev_ovl = nullptr;
   ccrdt::DevBuf first_list, ovl;
   ccrdt::DevBuf hbm_scratch;    // tier 4's per-wave working sets
+  // batched value/1 (value_kernels.hip): per listed key its |Observed| and the
+  // scan's scratch, the handed-on list (count first), and the host variant's
+  // uploaded keys and device-side result
+  ccrdt::DevBuf val_cnt, val_caps, val_part, val_list, val_keys, val_ptr, val_id, val_score;
   int trmv_first_tier = 0;
   uint64_t last_n_ops = 0;
   uint64_t trmv_tot[2][3] = {};  // per side: bound on (players, pool, rows) held

@@ -273,6 +273,24 @@ class _Engine:
         check(lib.ccrdt_engine_handed_on(self.h, tier, ptr(out), n.value, C.byref(n)), "handed_on")
         return out
 
+    def _values(self, name: str, keys):
+        """ccrdt_<name>_value over `keys` (None: every key): (ptr uint64[n + 1],
+        id int64, score int64), each key's pairs ranked by cmp/2."""
+        if keys is None:
+            n, kp = self.n_keys, None
+        else:
+            keys = np.asarray(keys)
+            if keys.dtype != np.uint64:  # (a negative index wraps and is refused as out of range)
+                keys = keys.astype(np.int64).astype(np.uint64)
+            keys = _c(keys, np.uint64).reshape(-1)
+            n, kp = int(keys.shape[0]), ptr(keys)
+        tot = C.c_int64()
+        check(getattr(lib, f"ccrdt_{name}_value_size")(self.h, n, kp, C.byref(tot)), f"{name}_value_size")
+        p = np.zeros(n + 1, np.uint64)
+        i, s = np.zeros(max(tot.value, 1), np.int64), np.zeros(max(tot.value, 1), np.int64)
+        check(getattr(lib, f"ccrdt_{name}_value")(self.h, n, kp, ptr(p), ptr(i), ptr(s)), f"{name}_value")
+        return p, i[:tot.value], s[:tot.value]
+
     def close(self):
         if getattr(self, "h", None):
             lib.ccrdt_engine_destroy(self.h)
@@ -369,6 +387,20 @@ class TopkRmvEngine(_Engine):
         (op, kind, id, score, dc, ts, vc...) and their count (device uint32)."""
         check(lib.ccrdt_trmv_extras_device(self.h, d_rows, cap_rows, d_count), "extras_device")
 
+    def values(self, keys=None):
+        """value/1 (topk_rmv.erl:91-95) of `keys` (key indices in any order,
+        repeats allowed; None: every key) read on the device: (ptr, id, score),
+        segment i = Observed of keys[i] as {Id, Score} ranked by cmp/2
+        (:390-395: Score descending, then Id descending)."""
+        return self._values("trmv", keys)
+
+    def values_device(self, n: int, d_keys: int | None, d_ptr: int, d_id: int, d_score: int,
+                      cap_entries: int) -> None:
+        """Enqueue values() of n keys (device uint64[n] at d_keys, None: key i
+        = i) into device arrays: d_ptr uint64[n + 1] always complete, d_id /
+        d_score int64[cap_entries] written for every key that fits whole."""
+        check(lib.ccrdt_trmv_value_device(self.h, n, d_keys, d_ptr, d_id, d_score, cap_entries), "values_device")
+
     def exchange_pack(self, d_pack: int, cap_rows: int, d_op_map: int | None, n_map: int, host_word: int) -> None:
         """Enqueue this rank's whole exchange pack [word | Vc | rows] at d_pack
         (ccrdt_trmv_exchange_pack): extras with global ops, count and host_word
@@ -441,8 +473,8 @@ class TopkRmvEngine(_Engine):
     def value(self, key: int) -> list[tuple[int, int]]:
         """value/1 of one key (topk_rmv.erl:91-95): [(Id, Score)] of Observed,
         sorted by Id (the reference's list order is map-iteration order, Q7)."""
-        st = self.export_range(key, key + 1)
-        return [(int(i), int(s)) for i, s in zip(st.obs_id, st.obs_score)]
+        _, i, s = self.values([key])
+        return sorted(zip(i.tolist(), s.tolist()))
 
     def downstream(self, key, op, id, score, dc, ts):
         """downstream/2 probes (topk_rmv.erl:102-124).  op 0 add, 1 rmv.

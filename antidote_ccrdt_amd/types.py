@@ -179,6 +179,19 @@ class LeaderboardEngine(_Engine):
         ops = _lib.LbOps(d.n, d["key_ptr"], d["kind"], d["id"], d["score"])
         check(lib.ccrdt_lb_apply_device(self.h, C.byref(ops)), "lb_apply_device")
 
+    def values(self, keys=None):
+        """value/1 (leaderboard.erl:84-86) of `keys` (board indices in any
+        order, repeats allowed; None: every board) read on the device: (ptr,
+        id, score), segment i = Observed of keys[i] as {Id, Score} ranked by
+        cmp/2 (:290-294: Score descending, then Id descending)."""
+        return self._values("lb", keys)
+
+    def values_device(self, n: int, d_keys: int | None, d_ptr: int, d_id: int, d_score: int,
+                      cap_entries: int) -> None:
+        """Enqueue values() of n boards into device arrays (as
+        TopkRmvEngine.values_device)."""
+        check(lib.ccrdt_lb_value_device(self.h, n, d_keys, d_ptr, d_id, d_score, cap_entries), "values_device")
+
     def sizes(self):
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         check(lib.ccrdt_lb_state_sizes(self.h, C.byref(a), C.byref(b), C.byref(c)), "lb_sizes")

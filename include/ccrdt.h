@@ -225,6 +225,28 @@ int ccrdt_trmv_replica_vc_device(ccrdt_engine* e, int64_t* d_out);
  * vc...}, grouped by key (order by op to get stream order); *d_count
  * (device) = how many there were (rows past cap_rows are not written). */
 int ccrdt_trmv_extras_device(ccrdt_engine* e, int64_t* d_rows, int64_t cap_rows, uint32_t* d_count);
+/* value/1 (topk_rmv.erl:91-95) of n keys at once, ranked.  keys[i] is a key
+ * index, in any order, repeats allowed (each occurrence gets its own
+ * segment); keys == NULL means key i = i (n <= n_keys).  Segment i (entries
+ * ptr[i] .. ptr[i + 1], ptr[n + 1] a CSR over entries) = Observed of keys[i]
+ * as {Id, Score}, ordered by cmp/2 (topk_rmv.erl:390-395): Score descending,
+ * then Id descending (inside Observed Ids are unique, so Ts never decides).
+ * Only the Observed pairs are read on the device and only they cross to the
+ * host; a fresh or reset engine gives all-empty segments.
+ * Host variants: _value_size gives the entry count to size id / score for;
+ * a key index outside [0, n_keys), n < 0 or a NULL output is CCRDT_EINVAL
+ * (nothing written, the engine stays usable); n == 0 is valid (ptr[0] = 0).
+ * _value_device: every pointer is device memory; the call is enqueued on the
+ * engine stream (after a preceding apply_device) and does not wait for the
+ * device.  d_ptr[0 .. n] is always written in full (d_ptr[n] = the true
+ * total); a key's entries are written only if the whole key fits
+ * (d_ptr[i + 1] <= cap_entries), nothing at or past cap_entries is touched;
+ * an out-of-range key yields an empty segment and reads nothing. */
+int ccrdt_trmv_value_size(ccrdt_engine* e, int64_t n, const uint64_t* keys, int64_t* n_entries);
+int ccrdt_trmv_value(ccrdt_engine* e, int64_t n, const uint64_t* keys, uint64_t* ptr, int64_t* id,
+                     int64_t* score);
+int ccrdt_trmv_value_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys, uint64_t* d_ptr, int64_t* d_id,
+                            int64_t* d_score, int64_t cap_entries);
 /* One rank's exchange pack in one call (both steps above, no host wait):
  * d_pack = [word | Vc[n_dc] | rows[cap_rows][6 + n_dc]] (int64, device), word
  * = extra-effect count (bits 0-31) | host_word << 32; a row's op is mapped
@@ -425,6 +447,13 @@ int ccrdt_lb_fetch_extra(ccrdt_engine* e, ccrdt_lb_extra* extra);
  * any order (op gives stream order); *d_count (device) = how many there were.
  * The replication step ships these without a host round trip. */
 int ccrdt_lb_extras_device(ccrdt_engine* e, int64_t* d_rows, int64_t cap_rows, uint32_t* d_count);
+/* value/1 (leaderboard.erl:84-86) of n boards at once, ranked by cmp/2
+ * (:290-294: Score descending, then Id descending); arguments, errors and
+ * the device variant's capacity rule as ccrdt_trmv_value*. */
+int ccrdt_lb_value_size(ccrdt_engine* e, int64_t n, const uint64_t* keys, int64_t* n_entries);
+int ccrdt_lb_value(ccrdt_engine* e, int64_t n, const uint64_t* keys, uint64_t* ptr, int64_t* id, int64_t* score);
+int ccrdt_lb_value_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys, uint64_t* d_ptr, int64_t* d_id,
+                          int64_t* d_score, int64_t cap_entries);
 /* leaderboard() = {Observed, Masked, Bans, Min, Size} (:62-68), canonical
  * (each list sorted by Id). */
 typedef struct {
