@@ -27,38 +27,6 @@ namespace ccrdt {
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 
-int trmv_launch_scan(const TrmvApplyArgs& a, uint64_t* partials, uint32_t* key_rmv, hipStream_t st);
-void trmv_kernels_preload();
-void trmv_wave_preload();
-void trmv_resident_preload();
-void trmv_steady_preload();
-int trmv_launch_validate(const TrmvApplyArgs& a, uint64_t n_ops, uint32_t* err, unsigned long long* scratch,
-                         hipStream_t st);
-int trmv_launch_mark_done(uint8_t* done, uint64_t n_keys, const uint32_t* list, uint32_t n_list, const uint32_t* n_dev,
-                          uint32_t* ex_cnt, hipStream_t st);
-int trmv_launch_keep(const TrmvApplyArgs& a, uint32_t grid, hipStream_t st);
-int trmv_launch_downstream(const TrmvDownArgs& a, hipStream_t st);
-int trmv_launch_wave(const TrmvApplyArgs& a, uint64_t grid_keys, hipStream_t st);
-int trmv_launch_first_list(const uint64_t* key_ptr, uint64_t n_keys, uint32_t thresh, uint32_t* list,
-                           uint32_t* count, hipStream_t st);
-uint32_t trmv_wave_waves(uint64_t grid_keys);
-int trmv_launch_resident_consume(const TrmvApplyArgs& a, uint32_t waves, hipStream_t st);
-int trmv_launch_steady(const TrmvApplyArgs& a, int cls, uint64_t grid_keys, hipStream_t st);
-int trmv_launch_resident(const TrmvApplyArgs& a, uint64_t grid_keys, hipStream_t st);
-int trmv_launch_steady_hbm(const TrmvApplyArgs& a, uint32_t waves, void* scratch, hipStream_t st);
-uint64_t trmv_steady_hbm_bytes(bool ranked);
-uint32_t trmv_steady_hbm_players();
-int trmv_launch_replica_vc(const int64_t* vc, uint64_t n_keys, int n_dc, int64_t* out,
-                           hipStream_t st);
-int trmv_launch_pack_extras(const uint64_t* key_ptr, const uint32_t* ex_cnt, const TrmvExtraRec* ex,
-                            const int64_t* ex_vc, uint64_t n_keys, int n_dc, int64_t* rows,
-                            int64_t cap, uint32_t* count, hipStream_t st);
-int trmv_launch_exchange_pack(const int64_t* vc, const uint64_t* key_ptr, const uint32_t* ex_cnt,
-                              const TrmvExtraRec* ex, const int64_t* ex_vc, uint64_t n_keys, int n_dc, int64_t* pack,
-                              int64_t cap, const int64_t* op_map, int64_t n_map, uint32_t host_word, hipStream_t st);
-int trmv_launch_exchange_reduce(const int64_t* g, int world, int64_t len, int n_dc, int64_t* hdr, int64_t* out,
-                                hipStream_t st);
-
 // Tiers of the apply chain: 0 = trmv_wave (tier 0), 1 / 2 = trmv_steady with
 // up to 256 / 1024 players per key (tier S, LDS), 3 = trmv_resident (tier R),
 // 4 = trmv_steady's HBM class (up to trmv_steady_hbm_players() players).  A

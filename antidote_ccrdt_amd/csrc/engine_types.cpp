@@ -13,42 +13,6 @@
 #include "engine.hpp"
 #include "types_kernels.hpp"
 
-namespace ccrdt {
-int avg_launch_apply(const AvgArgs& a, hipStream_t st);
-int avg_launch_value(const int64_t* sum, const int64_t* num, int64_t n_keys, int fresh, double* out,
-                     uint8_t* defined, hipStream_t st);
-int topk_launch_apply(const TopkArgs& a, int cls, uint64_t n_work, hipStream_t st);
-int topk_launch_value(const TopkValueArgs& a, int cls, uint64_t n_work, hipStream_t st);
-int lb_launch_apply(const LbArgs& a, int cls, uint64_t n_work, hipStream_t st);
-int lb_launch_downstream(const LbDownArgs& a, hipStream_t st);
-int lb_launch_pack_extras(const uint64_t* key_ptr, const uint32_t* ex_cnt, const LbExtraRec* ex, uint64_t n_keys,
-                          int64_t* rows, int64_t cap, uint32_t* count, hipStream_t st);
-int launch_ovf_need(const uint32_t* list, uint64_t n, const uint64_t* key_ptr, const uint32_t* cnt,
-                    uint32_t stride, uint64_t* need, hipStream_t st);
-int launch_caps_scan(const uint64_t* key_ptr, const uint32_t* cnt, uint32_t stride, uint64_t n,
-                     uint64_t* caps, uint64_t* off, uint64_t* part, hipStream_t st);
-int wc_launch_count(const uint64_t* doc_off, const uint8_t* bytes, uint64_t n_docs, uint64_t* ntok,
-                    hipStream_t st);
-int wc_launch_doc_key(const uint64_t* key_ptr, uint64_t n_keys, uint64_t n_docs, uint64_t* doc_key,
-                     hipStream_t st);
-int wc_launch_insert(const WcArgs& a, uint64_t n_tiles, hipStream_t st);
-int wc_launch_verify(const WcArgs& a, uint64_t n_tiles, hipStream_t st);
-int wc_launch_persist(const WcArgs& a, uint8_t* arena, unsigned long long* top, hipStream_t st);
-int wc_launch_owner_count(const WcArgs& a, uint32_t world, uint32_t* owner, unsigned long long* cur, hipStream_t st);
-int wc_launch_owner_scatter(const WcArgs& a, const uint32_t* owner, unsigned long long* cur, int64_t* meta,
-                            uint8_t* out, uint32_t world, hipStream_t st);
-int wc_launch_meta_split(const int64_t* meta, uint64_t n, uint64_t* wkey, int64_t* wcnt, uint32_t* wlen,
-                         hipStream_t st);
-int wc_launch_merge(const WcArgs& a, const uint64_t* wkey, const uint64_t* woff, const int64_t* cnt, uint64_t n,
-                    int verify, hipStream_t st);
-int wc_launch_check(const WcArgs& a, uint32_t n, hipStream_t st);
-int wc_launch_dl(const WcArgs& a, uint64_t n_docs, uint32_t passes, hipStream_t st);
-int wc_launch_cl_count(const WcClArgs& c, hipStream_t st);
-int wc_launch_cl_sum(const WcClArgs& c, hipStream_t st);
-int wc_launch_rehash(const WcSlot* old, const WcMeta* oldm, const unsigned long long* ocnt, uint64_t on, const WcArgs& a,
-                     hipStream_t st);
-}  // namespace ccrdt
-
 using namespace ccrdt;
 
 static int copy_buf(DevBuf& dst, const DevBuf& src, hipStream_t st) {

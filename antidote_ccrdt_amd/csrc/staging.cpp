@@ -21,11 +21,6 @@
 
 namespace ccrdt {
 
-int launch_widen_i64(int64_t* dst, const int32_t* src, const int64_t* base, const uint8_t* kind,
-                     uint64_t n, uint64_t chunk, hipStream_t st);
-int launch_widen_ops(int64_t* id, int64_t* score, int64_t* ts, const int32_t* src, const int64_t* base,
-                     const uint8_t* kind, uint64_t n, uint64_t chunk, hipStream_t st);
-
 namespace {
 constexpr int STAGE_THREADS = 16;                       // (at most; see stage_threads)
 constexpr uint64_t STAGE_CHUNK = 16ull << 20;          // bytes per slot

@@ -165,8 +165,6 @@ __global__ __launch_bounds__(256) void trmv_pack_rows_kernel(const uint64_t* key
   }
 }
 
-int trmv_launch_replica_vc(const int64_t* vc, uint64_t n_keys, int n_dc, int64_t* out, hipStream_t st);
-
 int trmv_launch_exchange_pack(const int64_t* vc, const uint64_t* key_ptr, const uint32_t* ex_cnt,
                               const TrmvExtraRec* ex, const int64_t* ex_vc, uint64_t n_keys, int n_dc, int64_t* pack,
                               int64_t cap, const int64_t* op_map, int64_t n_map, uint32_t host_word, hipStream_t st) {

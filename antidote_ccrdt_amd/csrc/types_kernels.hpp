@@ -1,7 +1,11 @@
-// types_kernels.hpp — argument blocks of the average / topk / leaderboard /
-// wordcount kernels and the generic segment scan.
+// types_kernels.hpp — argument blocks and launchers of the average / topk /
+// leaderboard / wordcount kernels and the generic segment scan, grouped by
+// type.  Each launcher is declared here only; the .hip that defines it
+// includes this header, so the compiler checks the two against each other.
 #pragma once
 #include <cstdint>
+
+#include "common.hpp"
 
 namespace ccrdt {
 
@@ -19,6 +23,9 @@ struct AvgArgs {
   int32_t fresh;
   uint32_t* status;
 };
+int avg_launch_apply(const AvgArgs& a, hipStream_t st);
+int avg_launch_value(const int64_t* sum, const int64_t* num, int64_t n_keys, int fresh, double* out,
+                     uint8_t* defined, hipStream_t st);
 
 // topk: per key a segment of (id, score) entries (any order)
 struct TopkArgs {
@@ -62,6 +69,8 @@ struct TopkValueArgs {
   int64_t* g_id;
   int64_t* g_score;
 };
+int topk_launch_apply(const TopkArgs& a, int cls, uint64_t n_work, hipStream_t st);
+int topk_launch_value(const TopkValueArgs& a, int cls, uint64_t n_work, hipStream_t st);
 
 // leaderboard: per board a segment of entries (id, score, status) + meta
 enum : uint8_t { LB_OBS = 0, LB_MASKED = 1, LB_BANNED = 2 };
@@ -125,6 +134,10 @@ struct LbDownArgs {
   const uint8_t* est;
   int32_t fresh;
 };
+int lb_launch_apply(const LbArgs& a, int cls, uint64_t n_work, hipStream_t st);
+int lb_launch_downstream(const LbDownArgs& a, hipStream_t st);
+int lb_launch_pack_extras(const uint64_t* key_ptr, const uint32_t* ex_cnt, const LbExtraRec* ex, uint64_t n_keys,
+                          int64_t* rows, int64_t cap, uint32_t* count, hipStream_t st);
 
 // wordcount / worddocumentcount
 constexpr uint64_t WC_TILE = 4096;  // bytes of a document per wave step (64 per lane)
@@ -250,5 +263,32 @@ struct WcClArgs {
   unsigned long long* t_cnt;
   uint32_t* status;
 };
+int wc_launch_count(const uint64_t* doc_off, const uint8_t* bytes, uint64_t n_docs, uint64_t* ntok,
+                    hipStream_t st);
+int wc_launch_doc_key(const uint64_t* key_ptr, uint64_t n_keys, uint64_t n_docs, uint64_t* doc_key,
+                     hipStream_t st);
+int wc_launch_insert(const WcArgs& a, uint64_t n_chunks, hipStream_t st);
+int wc_launch_verify(const WcArgs& a, uint64_t n_chunks, hipStream_t st);
+int wc_launch_persist(const WcArgs& a, uint8_t* arena, unsigned long long* top, hipStream_t st);
+int wc_launch_owner_count(const WcArgs& a, uint32_t world, uint32_t* owner, unsigned long long* cur, hipStream_t st);
+int wc_launch_owner_scatter(const WcArgs& a, const uint32_t* owner, unsigned long long* cur, int64_t* meta,
+                            uint8_t* out, uint32_t world, hipStream_t st);
+int wc_launch_meta_split(const int64_t* meta, uint64_t n, uint64_t* wkey, int64_t* wcnt, uint32_t* wlen,
+                         hipStream_t st);
+int wc_launch_merge(const WcArgs& a, const uint64_t* wkey, const uint64_t* woff, const int64_t* cnt, uint64_t n,
+                    int verify, hipStream_t st);
+int wc_launch_check(const WcArgs& a, uint32_t n, hipStream_t st);
+int wc_launch_dl(const WcArgs& a, uint64_t n_docs, uint32_t passes, hipStream_t st);
+int wc_launch_cl_count(const WcClArgs& c, hipStream_t st);
+int wc_launch_cl_sum(const WcClArgs& c, hipStream_t st);
+int wc_launch_rehash(const WcSlot* old, const WcMeta* oldm, const unsigned long long* ocnt, uint64_t on,
+                     const WcArgs& a, hipStream_t st);
+
+// generic segment scan: caps[k] = cnt[k * stride] + ops of key k, off = its
+// exclusive scan; need[w] of the keys an LDS class handed on
+int launch_caps_scan(const uint64_t* key_ptr, const uint32_t* cnt, uint32_t stride, uint64_t n,
+                     uint64_t* caps, uint64_t* off, uint64_t* part, hipStream_t st);
+int launch_ovf_need(const uint32_t* list, uint64_t n, const uint64_t* key_ptr, const uint32_t* cnt,
+                    uint32_t stride, uint64_t* need, hipStream_t st);
 
 }  // namespace ccrdt

@@ -30,9 +30,6 @@
 
 namespace ccrdt {
 
-int launch_caps_scan(const uint64_t* key_ptr, const uint32_t* cnt, uint32_t stride, uint64_t n,
-                     uint64_t* caps, uint64_t* off, uint64_t* part, hipStream_t st);
-
 namespace {
 
 // A listed key's source segment: `count` players (topk_rmv) or board entries
