@@ -153,6 +153,7 @@ def _setup_types(l):
     l.orc_lb_apply_mt.argtypes = [P, P, P, P, P, P, P, P, INT]
     l.orc_lb_sizes.argtypes = [P, P, P, P]
     l.orc_lb_export.argtypes = [P] + [P] * 11
+    l.orc_lb_import.argtypes = [P] + [P] * 11
     l.orc_lb_downstream.argtypes = [P, I64, P, P, P, P, P]
     l.orc_lb_cmp.restype = INT
     l.orc_lb_cmp.argtypes = [INT, I64, I64, INT, I64, I64]
@@ -215,6 +216,10 @@ class TopkOracle:
         return p, i, s
 
 
+LB_FIELDS = ("obs_ptr", "obs_id", "obs_score", "m_ptr", "m_id", "m_score", "b_ptr", "b_id",
+             "min_valid", "min_id", "min_score")
+
+
 class LbOracle:
     def __init__(self, n_keys, k=100, n_threads: int = 1):
         """n_threads > 1: apply() splits the boards over threads (configs[3]-sized tests)."""
@@ -247,11 +252,19 @@ class LbOracle:
                   m_id=z(m.value, np.int64), m_score=z(m.value, np.int64),
                   b_ptr=z(nk + 1, np.uint64), b_id=z(b.value, np.int64),
                   min_valid=z(nk, np.uint8), min_id=z(nk, np.int64), min_score=z(nk, np.int64))
-        tlib().orc_lb_export(self.h, *[_p(st[f]) for f in
-                                       ("obs_ptr", "obs_id", "obs_score", "m_ptr", "m_id",
-                                        "m_score", "b_ptr", "b_id", "min_valid", "min_id",
-                                        "min_score")])
+        tlib().orc_lb_export(self.h, *[_p(st[f]) for f in LB_FIELDS])
         return st
+
+    def import_state(self, st) -> None:
+        """The arrays of export() (a dict, or an object with the same fields)
+        read back: obs, masked, bans and min of every board set verbatim, no
+        invariant checked."""
+        g = (lambda f: st[f]) if isinstance(st, dict) else (lambda f: getattr(st, f))
+        dt = {"obs_ptr": np.uint64, "m_ptr": np.uint64, "b_ptr": np.uint64, "min_valid": np.uint8}
+        # (an empty array still needs an address)
+        arrs = [_a(g(f), dt.get(f, np.int64)) for f in LB_FIELDS]
+        arrs = [a if a.shape[0] else np.zeros(1, a.dtype) for a in arrs]
+        tlib().orc_lb_import(self.h, *[_p(a) for a in arrs])
 
     def downstream(self, key, op, id, score):
         key = _a(key, np.uint64)

@@ -350,6 +350,27 @@ void orc_lb_export(void* h, uint64_t* obs_ptr, int64_t* obs_id, int64_t* obs_sco
     min_score[k] = l.min ? l.min->score : 0;
   }
 }
+// The arrays of orc_lb_export read back: Observed, Masked, Bans and Min of
+// every board are set verbatim (no invariant is checked, so a state update/2
+// cannot reach -- Min not the minimum, a Masked pair above an Observed one --
+// can be given to add/3 and ban/2).
+void orc_lb_import(void* h, const uint64_t* obs_ptr, const int64_t* obs_id, const int64_t* obs_score,
+                   const uint64_t* m_ptr, const int64_t* m_id, const int64_t* m_score, const uint64_t* b_ptr,
+                   const int64_t* b_id, const uint8_t* min_valid, const int64_t* min_id,
+                   const int64_t* min_score) {
+  auto* s = (LbSet*)h;
+  for (size_t k = 0; k < s->keys.size(); ++k) {
+    Leaderboard& l = s->keys[k];
+    l.obs.clear();
+    l.masked.clear();
+    l.bans.clear();
+    for (uint64_t j = obs_ptr[k]; j < obs_ptr[k + 1]; ++j) l.obs[obs_id[j]] = obs_score[j];
+    for (uint64_t j = m_ptr[k]; j < m_ptr[k + 1]; ++j) l.masked[m_id[j]] = m_score[j];
+    for (uint64_t j = b_ptr[k]; j < b_ptr[k + 1]; ++j) l.bans.insert(b_id[j]);
+    if (min_valid[k]) l.min = LPair{min_id[k], min_score[k]};
+    else l.min.reset();
+  }
+}
 // op 0 add, 1 ban; out 0 add, 1 add_r, 2 ban, 255 noop
 void orc_lb_downstream(void* h, int64_t n, const uint64_t* key, const uint8_t* op, const int64_t* id,
                        const int64_t* score, uint8_t* out) {

@@ -146,3 +146,81 @@ def test_lb_oracle_threads_match_sequential():
         assert np.array_equal(xa[f], xb[f])
     sa, sb = a.export(), b.export()
     assert all(np.array_equal(sa[f], sb[f]) for f in sa)
+
+
+def _lb_state(obs, masked, bans, mn):
+    """The export() layout of one board from plain dicts."""
+    o, m = sorted(obs), sorted(masked)
+    a = lambda v, dt=np.int64: np.array(v, dt)
+    return dict(obs_ptr=a([0, len(o)], np.uint64), obs_id=a(o), obs_score=a([obs[i] for i in o]),
+                m_ptr=a([0, len(m)], np.uint64), m_id=a(m), m_score=a([masked[i] for i in m]),
+                b_ptr=a([0, len(bans)], np.uint64), b_id=a(sorted(bans)),
+                min_valid=a([1 if mn else 0], np.uint8), min_id=a([mn[0] if mn else 0]),
+                min_score=a([mn[1] if mn else 0]))
+
+
+def test_lb_oracle_import_roundtrip():
+    """export -> import_state -> export is the identity (boards with Masked
+    entries and bans, an empty board among them), and the imported oracle
+    goes on as the exporting one does."""
+    rng = np.random.default_rng(41)
+    nk, n = 6, 3000
+    key = np.sort(rng.integers(0, nk - 1, n))  # (the last board stays empty)
+    kp = np.searchsorted(key, np.arange(nk + 1)).astype(np.uint64)
+    kind = np.where(rng.random(n) < 0.05, 2, rng.integers(0, 2, n)).astype(np.uint8)
+    pid, sc = rng.integers(0, 200, n, dtype=np.int64), rng.integers(0, 1000, n, dtype=np.int64)
+    a, b = orc.LbOracle(nk, 10), orc.LbOracle(nk, 10)
+    a.apply(kp, kind, pid, sc)
+    st = a.export()
+    assert st["m_id"].shape[0] and st["b_id"].shape[0] and st["obs_ptr"][-1] == st["obs_ptr"][-2]
+    b.import_state(st)
+    st2 = b.export()
+    assert all(np.array_equal(st[f], st2[f]) for f in st)
+    xa, xb = a.apply(kp, kind[::-1], pid[::-1], sc), b.apply(kp, kind[::-1], pid[::-1], sc)
+    assert all(np.array_equal(xa[f], xb[f]) for f in xa)
+    sa, sb = a.export(), b.export()
+    assert all(np.array_equal(sa[f], sb[f]) for f in sa)
+
+
+def test_lb_oracle_import_min_not_minimum():
+    """add/3 and ban/2 worked by hand (leaderboard.erl) on an imported state
+    whose Min is an Observed pair but not min/1 of Observed: Size 4, Observed
+    {1:50, 2:40, 3:30, 4:20}, Masked {5:10}, Min = {2, 40}."""
+    obs, masked, mn = {1: 50, 2: 40, 3: 30, 4: 20}, {5: 10}, (2, 40)
+
+    def fresh(masked=masked):
+        o = orc.LbOracle(1, 4)
+        o.import_state(_lb_state(obs, masked, [], mn))
+        assert lb_state_key(o.export()) == lb_state_key(_lb_state(obs, masked, [], mn))
+        return o
+
+    # add {6, 35}: not banned (:217), not Observed (:220), Observed full (:233),
+    # cmp({6,35}, Min = {2,40}) is false (:235, :293: 35 > 40 fails) although
+    # {6,35} beats the true minimum {4,20}: it goes to Masked (:243-248), Min stays.
+    o = fresh()
+    x = o.apply(*lb_batch([["add", 6, 35]]))
+    assert x["kind"][0] == 255
+    assert lb_state_key(o.export()) == {"obs": [[1, 50], [2, 40], [3, 30], [4, 20]],
+                                        "masked": [[5, 10], [6, 35]], "bans": [], "min": [2, 40]}
+    # add {7, 45}: cmp({7,45}, {2,40}) is true (:235): {7,45} enters Observed
+    # (:238), MinId = 2 leaves it (:239) for Masked with MinScore (:240), and
+    # Min := min(NewObserved) = {4, 20} (:241, :297-303).
+    x = o.apply(*lb_batch([["add", 7, 45]]))
+    assert x["kind"][0] == 255
+    assert lb_state_key(o.export()) == {"obs": [[1, 50], [3, 30], [4, 20], [7, 45]],
+                                        "masked": [[2, 40], [5, 10], [6, 35]], "bans": [], "min": [4, 20]}
+    # ban 4 (the true minimum, not MinId) on the imported state: 4 is Observed
+    # (:269), get_largest(Masked) = {5,10} (:271, :306-312) is promoted
+    # (:280-281), Min := {5,10} (:282), extra effect {add, {5,10}} (:283).
+    o = fresh()
+    x = o.apply(*lb_batch([["ban", 4]]))
+    assert (int(x["kind"][0]), int(x["id"][0]), int(x["score"][0])) == (0, 5, 10)
+    assert lb_state_key(o.export()) == {"obs": [[1, 50], [2, 40], [3, 30], [5, 10]], "masked": [],
+                                        "bans": [4], "min": [5, 10]}
+    # the same ban with Masked empty: get_largest is {nil,nil} (:273), MinId = 2
+    # is not the banned Id, so Min stays {2, 40} (:274-277), no extra effect.
+    o = fresh(masked={})
+    x = o.apply(*lb_batch([["ban", 4]]))
+    assert x["kind"][0] == 255
+    assert lb_state_key(o.export()) == {"obs": [[1, 50], [2, 40], [3, 30]], "masked": [], "bans": [4],
+                                        "min": [2, 40]}
