@@ -710,6 +710,9 @@ int trmv_pass_full(Engine& E, TrmvApplyArgs a, uint64_t n_ops, uint32_t* status,
   // layout's totals, its free space cut into TRMV_NSUB sub-arenas.  The
   // device copy of the table is made by the next in-place pass (arena_pending),
   // so a fresh batch that no resident batch follows pays no round trip for it.
+  // a fresh roomy layout: no VALID capacity record on a key with a wide add
+  // Score (tier 0 writes one for every key it applies; see the kernel)
+  if (E.fresh && a.slack && nk) CCRDT_TRY(trmv_launch_wide_cap(a, nk, E.stream));
   const bool roomy = a.slack != 0 && (first_tier == 3 || first_tier == 0);
   if (roomy) {
     trmv_side_caps(E, out, E.arena_cap);

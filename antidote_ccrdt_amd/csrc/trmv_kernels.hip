@@ -458,11 +458,41 @@ int trmv_launch_first_list(const uint64_t* key_ptr, uint64_t n_keys, uint32_t th
   return CCRDT_OK;
 }
 
+// A fresh batch laid out with room (one wave per key): a key with an add Score
+// outside 32 bits loses its VALID capacity record.  Tier R keeps a player's
+// largest Score in 32 bits and meets the other elements' Scores only when it
+// lays a key out again; without the record the next in-place batch relocates
+// the key, meets the Score in the copy and hands the key on before its first
+// store -- appending to it instead, a rmv could leave the wide Score as its
+// player's largest.  (A pass of its own, on the roomy path only: tier 0 and
+// the tight layout of the headline batch are untouched.)
+__global__ __launch_bounds__(256) void trmv_wide_cap_kernel(const uint64_t* key_ptr, const uint8_t* kind,
+                                                            const int64_t* score, uint64_t n_keys, KeyCap* cap) {
+  const uint64_t k = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (k >= n_keys) return;  // (wave-uniform)
+  const uint64_t hi = key_ptr[k + 1];
+  bool w = false;
+  for (uint64_t o = key_ptr[k] + (uint64_t)lane_id(); o < hi; o += 64) {
+    const int64_t sc = score[o];
+    w |= kind[o] < 2 && sc != (int64_t)(int32_t)sc;
+  }
+  if (ballot(w) && lane_id() == 0) cap[k].flags = 0;
+}
+
+int trmv_launch_wide_cap(const TrmvApplyArgs& a, uint64_t n_keys, hipStream_t st) {
+  if (n_keys == 0) return CCRDT_OK;
+  hipLaunchKernelGGL(trmv_wide_cap_kernel, dim3((unsigned)((n_keys * 64 + 255) / 256)), dim3(256), 0, st, a.key_ptr,
+                     a.kind, a.score, n_keys, a.new_s.cap);
+  CCRDT_HIP(hipGetLastError());
+  return CCRDT_OK;
+}
+
 // ------------------------------------------------------------- launchers
 // (scratch: one u64 flag, zeroed here)
 void trmv_kernels_preload() {
   preload_kernels(trmv_scan_partials, trmv_scan_tops, trmv_scan_apply, trmv_validate_kernel, trmv_validate_rows_any,
-                  trmv_validate_rows_exact, trmv_keep_kernel, trmv_mark_done_kernel, trmv_first_list_kernel);
+                  trmv_validate_rows_exact, trmv_keep_kernel, trmv_mark_done_kernel, trmv_first_list_kernel,
+                  trmv_wide_cap_kernel);
 }
 
 int trmv_launch_validate(const TrmvApplyArgs& a, uint64_t n_ops, uint32_t* err, unsigned long long* scratch,

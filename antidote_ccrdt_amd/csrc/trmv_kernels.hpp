@@ -246,6 +246,8 @@ int trmv_launch_mark_done(uint8_t* done, uint64_t n_keys, const uint32_t* list, 
 int trmv_launch_keep(const TrmvApplyArgs& a, uint32_t grid, hipStream_t st);
 int trmv_launch_downstream(const TrmvDownArgs& a, hipStream_t st);
 int trmv_launch_wave(const TrmvApplyArgs& a, uint64_t grid_keys, hipStream_t st);
+// fresh batch laid out with room: keys with an add Score outside 32 bits lose their VALID capacity record
+int trmv_launch_wide_cap(const TrmvApplyArgs& a, uint64_t n_keys, hipStream_t st);
 int trmv_launch_first_list(const uint64_t* key_ptr, uint64_t n_keys, uint32_t thresh, uint32_t* list,
                            uint32_t* count, hipStream_t st);
 uint32_t trmv_wave_waves(uint64_t grid_keys);

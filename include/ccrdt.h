@@ -45,7 +45,14 @@ extern "C" {
 #define CCRDT_EKEYCAP 6 /* topk_rmv: the batch COMMITTED except for the keys
                            that would exceed the per-key capacity
                            (CCRDT_TRMV_MAX_PLAYERS players, 65535 Masked
-                           elements, 65534 Removals rows); those keep their
+                           elements, 65534 Removals rows; the element bound
+                           is taken before the batch is applied, whatever its
+                           rmvs remove: the key's Masked elements plus its ops
+                           in the batch, or plus its adds only where tier R
+                           applies the key (K <= 128, up to 256 players, Ids
+                           and Scores in 32 bits); a player has one
+                           Removals row, so the player bound is met before
+                           the row bound); those keep their
                            previous state, produce no extras, and are listed
                            by ccrdt_engine_handed_on(e, 4).  Their ops go to
                            the host (Erlang) path. */
