@@ -145,6 +145,48 @@ __device__ __forceinline__ uint32_t wave_excl_scan_u32(uint32_t v, uint32_t& tot
   total = rl32(inc, 63);
   return inc - v;
 }
+// v of the first active lane, as a wave-uniform (scalar) value.
+__device__ __forceinline__ uint32_t ufl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ int64_t ufl64(int64_t v) {
+  const uint32_t lo = ufl((uint32_t)v), hi = ufl((uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// Forward permute: lane i's v goes to lane dst (ds_permute).
+__device__ __forceinline__ uint32_t perm32(uint32_t v, uint32_t dst) {
+  return (uint32_t)__builtin_amdgcn_ds_permute((int)(dst << 2), (int)v);
+}
+// Stable sort of the wave by key bits [6, 6 + BITS) of kv (payload: low 6
+// bits); one ballot split per bit.
+template <int BITS>
+__device__ __forceinline__ uint32_t wave_radix_sort(uint32_t kv) {
+#pragma unroll
+  for (int b = 0; b < BITS; ++b) {
+    const bool bit = (kv >> (6 + b)) & 1u;
+    const uint64_t ones = ballot(bit);
+    const uint32_t nz = 64u - (uint32_t)__builtin_popcountll(ones);
+    const uint32_t dst = bit ? nz + mbcnt(ones) : mbcnt(~ones);
+    kv = perm32(kv, dst);
+  }
+  return kv;
+}
+// Inclusive max-scan over the 64 lanes (DPP row shifts, then row broadcasts;
+// identity 0): each lane gets the largest value at or below it.
+__device__ __forceinline__ uint32_t wave_incl_max_dpp(uint32_t v) {
+  uint32_t o;
+  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
+  v = o > v ? o : v;
+  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
+  v = o > v ? o : v;
+  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
+  v = o > v ? o : v;
+  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
+  v = o > v ? o : v;
+  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+  v = o > v ? o : v;
+  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+  v = o > v ? o : v;
+  return v;
+}
 // Inclusive prefix sum over the 64 lanes in 6 DPP adds (no LDS crossbar):
 // row_shr 1/2/4/8 scan each 16-lane row, row_bcast:15/31 carry the row
 // totals into the rows above.  Lanes a DPP source cannot reach add `old` = 0.

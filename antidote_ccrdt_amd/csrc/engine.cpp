@@ -11,8 +11,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <numeric>
 #include <string>
 #include <thread>
 #include <tuple>
@@ -34,11 +32,12 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 // 3 -> 1 -> 2 (tier R needs K <= 128; else 1 -> 2); only when tier 2 handed
 // keys on does the host launch tier 4 on them, after the chain's status read.
 // Tier 4 is last: the keys it hands on are over the per-key capacity
-// (CCRDT_EKEYCAP, ccrdt_engine_handed_on(e, 4)).
-static constexpr int TRMV_N_TIERS = 5;
-static constexpr int TRMV_TIER_LAST = 4;
+// (CCRDT_EKEYCAP, ccrdt_engine_handed_on(e, 4)).  The tiers and the other
+// slots of the per-batch tables are named in include/ccrdt.h
+// (CCRDT_TRMV_TIER_*, _SLOT_*, _MS_*).
+static constexpr int TRMV_N_TIERS = CCRDT_TRMV_N_TIERS;
+static constexpr int TRMV_TIER_LAST = CCRDT_TRMV_TIER_HBM;
 static constexpr uint32_t TRMV_HBM_WAVES = 128;  // workgroups (scratch slots) of tier 4
-static constexpr int TRMV_STATUS_WORDS = 2 + 2 * TRMV_N_TIERS;  // [0,2) scan, [2+2t, 4+2t) tier t
 static constexpr uint32_t TRMV_LATER_GRID = 4096;  // keys the grids of the later tiers cover
 
 // f(k0, k1) over [0, n) in contiguous ranges on up to 16 host threads (the
@@ -264,15 +263,13 @@ int ccrdt_engine_last_kernel_ms(ccrdt_engine* e, float* ms) {
 
 int ccrdt_engine_tier_ms(ccrdt_engine* e, int tier, float* ms) {
   if (!e || !ms) return CCRDT_EINVAL;
-  auto it = e->trmv_tier_ms.find(tier);
-  *ms = it == e->trmv_tier_ms.end() ? 0.f : it->second;
+  *ms = tier >= 0 && tier < CCRDT_TRMV_N_MS ? e->trmv_tier_ms[tier] : 0.f;
   return CCRDT_OK;
 }
 
 int ccrdt_engine_overflow_keys(ccrdt_engine* e, int slot_class, int64_t* n) {
   if (!e || !n) return CCRDT_EINVAL;
-  auto it = e->trmv_overflow_keys.find(slot_class);
-  *n = it == e->trmv_overflow_keys.end() ? 0 : it->second;
+  *n = slot_class >= 0 && slot_class < CCRDT_TRMV_N_SLOTS ? e->trmv_overflow_keys[slot_class] : 0;
   return CCRDT_OK;
 }
 
@@ -309,16 +306,141 @@ int trmv_err_code(uint32_t err) {
                                                                                                   : CCRDT_EINVAL;
 }
 
-// The pool's capacity factor of segments laid out for in-place growth
-// (a.slack): capacity = factor x (elements + the batch's ops) + 32, so later
-// batches append slabs in place (CCRDT_TRMV_POOL_SLACK = 2..8, tuning knob).
-int trmv_pool_slack() {
-  static const int v = [] {
-    const char* e = getenv("CCRDT_TRMV_POOL_SLACK");
-    const int x = e ? atoi(e) : 2;
-    return x < 2 ? 2 : (x > 8 ? 8 : x);
-  }();
-  return v;
+// The environment knobs of the apply chain, read once, on first use:
+//   CCRDT_TRMV_POOL_SLACK     2..8, default 2   the pool's capacity factor of segments laid out for
+//                                               in-place growth (a.slack): capacity = factor x
+//                                               (elements + the batch's ops) + 32, so later batches
+//                                               append slabs in place
+//   CCRDT_TRMV_FIRST_TIER     default -1        -1 = the default chain, 0 = tier 0 first (fresh
+//                                               batches only), 1 = tier S first, 3 = tier R first
+//                                               (resident batches only)
+//   CCRDT_TRMV_OVERLAP        on unless 0       the overlapped hand-on (trmv_head_overlapped)
+//   CCRDT_TRMV_OVERLAP_KEYS   default 2^18      the most keys of an engine that overlaps
+//   CCRDT_TRMV_OVERLAP_WAVES  1..4096, def. 32  tier R's waves beside tier 0 (32: 16 could not keep
+//                                               up with the hand-ons, 48 and 64 slowed tier 0)
+//   CCRDT_TRMV_INPLACE        on unless 0       0: every resident batch is a full rewrite (A/B knob)
+// and the hooks of the tests, read at every call (TrmvHooks: the tests set
+// them inside one process):
+//   CCRDT_TRMV_FAIL_FINISH=1    the full rewrite that finishes an in-place batch fails as an
+//                               allocation would (CCRDT_EPARTIAL's path)
+//   CCRDT_TRMV_OVERLAP_STALL=1  the overlapped head's consumers give up at once when no hand-on
+//                               is there yet, and the host's fallback runs
+//   CCRDT_TRMV_ARENA_ROOM=n     at most n free elements past the arena's top, so relocations run
+//                               out and the full rewrite that finishes a batch runs
+int env_int(const char* v, int dflt, int lo, int hi) { return std::clamp(v ? atoi(v) : dflt, lo, hi); }
+bool env_on(const char* v) { return !(v && v[0] == '0'); }
+bool env_is1(const char* v) { return v && v[0] == '1'; }
+uint64_t env_u64(const char* v, uint64_t dflt) { return v ? strtoull(v, nullptr, 10) : dflt; }
+struct TrmvKnobs {
+  int pool_slack = env_int(getenv("CCRDT_TRMV_POOL_SLACK"), 2, 2, 8);
+  int first_tier = env_int(getenv("CCRDT_TRMV_FIRST_TIER"), -1, INT32_MIN, INT32_MAX);
+  bool overlap = env_on(getenv("CCRDT_TRMV_OVERLAP"));
+  bool inplace = env_on(getenv("CCRDT_TRMV_INPLACE"));
+  uint64_t overlap_keys = env_u64(getenv("CCRDT_TRMV_OVERLAP_KEYS"), 1ull << 18);
+  uint32_t overlap_waves = (uint32_t)env_int(getenv("CCRDT_TRMV_OVERLAP_WAVES"), 32, 1, 4096);
+  static const TrmvKnobs& get() {
+    static const TrmvKnobs k;
+    return k;
+  }
+};
+struct TrmvHooks {  // (each one read where it is used, at every call, and only there)
+  static bool fail_finish() { return env_is1(getenv("CCRDT_TRMV_FAIL_FINISH")); }
+  static bool overlap_stall() { return env_is1(getenv("CCRDT_TRMV_OVERLAP_STALL")); }
+  static const char* arena_room() { return getenv("CCRDT_TRMV_ARENA_ROOM"); }  // (null: not set)
+};
+
+// The status block of a batch (E.status) and its last read-back (E.h_status).
+// Words: [0, 2) the capacity scan's, then one pair per tier t -- the keys it
+// handed on, the error bits of its ops -- which the tier's kernels address as
+// a.status[0] / [1]; 16 bytes of scratch for the validation follow the words.
+struct TrmvStatus {
+  static constexpr int TRMV_STATUS_WORDS = 2 + 2 * TRMV_N_TIERS;
+  static constexpr uint64_t ALLOC = TRMV_STATUS_WORDS * 4 + 16;  // (+ the validation's scratch flag)
+  uint32_t* dev;
+  uint32_t* host;
+  hipStream_t stream;
+  uint32_t* count(int t) const { return dev + 2 + 2 * t; }
+  // (the validation writes tier R's error word)
+  uint32_t* verr() const { return count(CCRDT_TRMV_TIER_RESIDENT) + 1; }
+  unsigned long long* vscratch() const { return reinterpret_cast<unsigned long long*>(dev + TRMV_STATUS_WORDS); }
+  hipError_t clear() const { return hipMemsetAsync(dev, 0, TRMV_STATUS_WORDS * 4, stream); }
+  hipError_t clear_tier(int t) const { return hipMemsetAsync(count(t), 0, 8, stream); }
+  // (sync = false: the caller queues more copies, then synchronises the stream)
+  hipError_t read_back(bool sync = true) const {
+    const hipError_t e = hipMemcpyAsync(host, dev, TRMV_STATUS_WORDS * 4, hipMemcpyDeviceToHost, stream);
+    return e != hipSuccess || !sync ? e : hipStreamSynchronize(stream);
+  }
+  // of the last read-back
+  uint32_t handed(int t) const { return host[2 + 2 * t]; }
+  uint32_t errors(int t) const { return host[3 + 2 * t]; }
+};
+
+// What one pass over the keys hands from step to step.
+struct TrmvRun {
+  Engine& E;
+  TrmvStatus st;
+  TrmvApplyArgs a;
+  uint64_t n_ops;
+  uint64_t tot[3] = {};           // elements of the new side's arrays (trmv_layout)
+  int chain[4] = {}, n_chain = 0, n_head = 0;  // the tiers in order; [0, n_head) is queued in one go
+  int prev = -1;     // the tier whose hand-on list the next tier takes (-1: every key)
+  int next_evt = 0;  // the next free slot of E.evt
+};
+
+// Records the pass's next boundary event, E.evt[r.next_evt], on the engine's
+// stream.  A pass needs at most 8: the in-place pass 3 (validation,
+// tier R, end); a full rewrite 3 for its head (start, two tiers at most: tier
+// 0 and tier R), 3 for the tail (start, tiers 1 and 2) and 2 around tier 4.
+// A full rewrite that finishes an in-place batch starts again at slot 0: the
+// in-place pass has read its intervals by then.
+int trmv_mark(TrmvRun& r) {
+  if (r.next_evt >= (int)(sizeof(r.E.evt) / sizeof(r.E.evt[0]))) {
+    set_error("trmv_apply: out of tier boundary events");
+    return CCRDT_EDEVICE;
+  }
+  CCRDT_HIP(hipEventRecord(r.E.evt[r.next_evt++], r.E.stream));
+  return CCRDT_OK;
+}
+
+// Points a at tier t's input -- every key (prev < 0), or the list tier prev
+// handed on, whose length the kernels read on the device unless the host
+// knows it (n_host) -- and at t's own hand-on list and status pair.
+void trmv_point(const Engine& E, const TrmvStatus& st, TrmvApplyArgs& a, int t, int prev, uint32_t n_host = 0) {
+  a.key_list = prev < 0 ? nullptr : E.tier_ovf[prev].as<uint32_t>();
+  a.n_list = prev < 0 ? (uint32_t)E.n_keys : n_host;
+  a.n_list_dev = prev < 0 || n_host ? nullptr : st.count(prev);
+  a.ovf_list = E.tier_ovf[t].as<uint32_t>();
+  a.status = st.count(t);
+}
+
+// One tier queued: its kernels over r.prev's hand-ons (trmv_point), then the
+// boundary event that ends its interval; the next tier takes its hand-ons.
+int trmv_tier_launch(TrmvRun& r, int t, uint32_t n_host = 0) {
+  Engine& E = r.E;
+  trmv_point(E, r.st, r.a, t, r.prev, n_host);
+  const uint64_t grid = r.prev < 0 ? (uint64_t)E.n_keys : std::min<uint64_t>((uint64_t)E.n_keys, TRMV_LATER_GRID);
+  if (t == CCRDT_TRMV_TIER_WAVE) CCRDT_TRY(trmv_launch_wave(r.a, grid, E.stream));
+  else if (t == CCRDT_TRMV_TIER_RESIDENT) CCRDT_TRY(trmv_launch_resident(r.a, grid, E.stream));
+  else if (t == CCRDT_TRMV_TIER_HBM)
+    CCRDT_TRY(trmv_launch_steady_hbm(r.a, std::min<uint32_t>(n_host, TRMV_HBM_WAVES), E.hbm_scratch.p, E.stream));
+  else CCRDT_TRY(trmv_launch_steady(r.a, t - CCRDT_TRMV_TIER_S256, grid, E.stream));
+  r.prev = t;
+  return trmv_mark(r);
+}
+
+// After a read-back, the n tiers whose intervals start at event e0: their
+// error bits as a code, else each one's time and hand-on count booked.
+int trmv_book(Engine& E, const TrmvStatus& st, const int* tiers, int n, int e0) {
+  uint32_t err = 0;
+  for (int i = 0; i < n; ++i) err |= st.errors(tiers[i]);
+  if (err) return trmv_err_code(err);
+  for (int i = 0; i < n; ++i) {
+    float ms = 0.f;
+    CCRDT_HIP(hipEventElapsedTime(&ms, E.evt[e0 + i], E.evt[e0 + i + 1]));
+    E.trmv_tier_ms[tiers[i]] += ms;
+    E.trmv_overflow_keys[tiers[i]] = st.handed(tiers[i]);
+  }
+  return CCRDT_OK;
 }
 
 // Capacities (elements) of a data side's arrays.
@@ -329,25 +451,60 @@ void trmv_side_caps(const Engine& E, int ds, uint64_t cap[3]) {
   cap[2] = E.n_dc ? b.r_vc.bytes / (8 * (uint64_t)E.n_dc) : 0;
 }
 
+// The in-place pass's pinned read-back buffer: the sub-arena counters, then the layout counts.
+constexpr size_t ARENA_RB = sizeof(Engine::arena_sub[0]);
+bool trmv_pin_arena(Engine& E) {
+  if (!E.h_arena && hipHostMalloc(&E.h_arena, 2 * ARENA_RB + 16 * TRMV_NSUB, hipHostMallocDefault) != hipSuccess)
+    E.h_arena = nullptr;
+  return E.h_arena != nullptr;
+}
+
+// The arena's use after an in-place pass (E.h_arena): what this pass took,
+// what is left; the next batch runs in place only while the room left covers
+// twice this pass's take.
+void trmv_arena_account(Engine& E) {
+  const uint64_t(*cnt)[3] = reinterpret_cast<const uint64_t(*)[3]>(E.h_arena);
+  bool roomy = true;
+  for (int x = 0; x < 3; ++x) {
+    uint64_t used = 0, room = 0;
+    for (int i = 0; i < TRMV_NSUB; ++i) {
+      const uint64_t c = std::min(cnt[i][x], E.arena_sub[1][i][x]);
+      used += c - E.arena_sub[0][i][x];
+      room += E.arena_sub[1][i][x] - c;
+    }
+    const uint64_t take = used - std::min(used, E.arena_used[x]);
+    E.arena_used[x] = used;
+    E.arena_rate[x] = std::max(E.arena_rate[x], take);
+    roomy &= room >= 2 * take;
+  }
+  E.inplace_ready = roomy;
+  // keys by layout: relocated, appended, compacted
+  const uint32_t* lc = reinterpret_cast<const uint32_t*>(static_cast<const char*>(E.h_arena) + 2 * ARENA_RB);
+  for (int l = 0; l < 3; ++l) {
+    uint32_t n = 0;
+    for (int i = 0; i < TRMV_NSUB; ++i) n += lc[4 * i + l];
+    E.trmv_overflow_keys[CCRDT_TRMV_SLOT_RELOCATED + l] = n;
+  }
+}
+
 // In place (tier R alone): the batch validated, then every key updated in
 // the data arrays it lives in (meta / cap ping-pong).  Keys that cannot be
 // updated in place (outside tier R's class, or the arena is full) are left
-// as they were and listed in tier_ovf[3]; *handed = their number.
-int trmv_pass_inplace(Engine& E, TrmvApplyArgs a, uint64_t n_ops, uint32_t* status, uint32_t& handed) {
+// as they were and listed in tier_ovf[3] (CCRDT_TRMV_SLOT_TO_REWRITE counts them).
+int trmv_pass_inplace(Engine& E, const TrmvApplyArgs& a0, uint64_t n_ops, const TrmvStatus& st) {
   const uint64_t nk = (uint64_t)E.n_keys;
-  const int D = E.n_dc;
   CCRDT_TRY(E.trmv[1 - E.mcur].meta.ensure(nk * sizeof(KeyMeta)));
   CCRDT_TRY(E.trmv[1 - E.mcur].cap.ensure(nk * sizeof(KeyCap)));
-  constexpr size_t ARENA_RB = sizeof(E.arena_sub[0]);  // (the counters; the layout counts follow the ends)
   // the readback's pinned buffer before anything is queued: a failure here
   // leaves the state untouched
-  if (!E.h_arena && hipHostMalloc(&E.h_arena, 2 * ARENA_RB + 16 * TRMV_NSUB, hipHostMallocDefault) != hipSuccess) {
-    E.h_arena = nullptr;
+  if (!trmv_pin_arena(E)) {
     set_error("trmv_apply: pinned allocation failed");
     return CCRDT_EDEVICE;
   }
+  TrmvRun r{E, st, a0, n_ops};
+  TrmvApplyArgs& a = r.a;
   a.inplace = 1;
-  a.slack = trmv_pool_slack();  // (relocations' pool capacity)
+  a.slack = TrmvKnobs::get().pool_slack;  // (relocations' pool capacity)
   a.old_s = E.trmv_side(E.mcur, E.cur);
   a.new_s = E.trmv_side(1 - E.mcur, E.cur);
   if (E.arena_pending) {  // the sub-arena table the last full pass laid out
@@ -358,90 +515,67 @@ int trmv_pass_inplace(Engine& E, TrmvApplyArgs a, uint64_t n_ops, uint32_t* stat
   a.arena_lim = E.arena.as<unsigned long long>() + 3 * TRMV_NSUB;
   a.lay_cnt = reinterpret_cast<uint32_t*>(E.arena.as<unsigned long long>() + 6 * TRMV_NSUB);
   CCRDT_HIP(hipMemsetAsync(a.lay_cnt, 0, 4 * TRMV_NSUB * sizeof(uint32_t), E.stream));
-  a.key_done = nullptr;
-  a.key_list = nullptr;
-  a.n_list = (uint32_t)nk;
-  a.n_list_dev = nullptr;
-  a.ovf_list = E.tier_ovf[3].as<uint32_t>();
-  a.status = status + 2 + 2 * 3;
-  a.verr = status + 2 + 2 * 3 + 1;  // (tier R's error word: the validation writes it)
-  CCRDT_HIP(hipEventRecord(E.evt[0], E.stream));
-  CCRDT_TRY(trmv_launch_validate(a, n_ops, status + 2 + 2 * 3 + 1,
-                                 reinterpret_cast<unsigned long long*>(status + TRMV_STATUS_WORDS), E.stream));
-  CCRDT_HIP(hipEventRecord(E.evt[1], E.stream));
-  CCRDT_TRY(trmv_launch_resident(a, nk, E.stream));
-  CCRDT_HIP(hipEventRecord(E.evt[2], E.stream));
-  CCRDT_HIP(hipMemcpyAsync(E.h_status, status, TRMV_STATUS_WORDS * 4, hipMemcpyDeviceToHost, E.stream));
+  a.verr = st.verr();
+  // (for the validation, which gets the args tier R gets: trmv_tier_launch points them again)
+  trmv_point(E, st, a, CCRDT_TRMV_TIER_RESIDENT, -1);
+  const int e0 = r.next_evt;
+  CCRDT_TRY(trmv_mark(r));
+  CCRDT_TRY(trmv_launch_validate(a, n_ops, st.verr(), st.vscratch(), E.stream));
+  CCRDT_TRY(trmv_mark(r));
+  CCRDT_TRY(trmv_tier_launch(r, CCRDT_TRMV_TIER_RESIDENT));
+  CCRDT_HIP(st.read_back(false));
   CCRDT_HIP(hipMemcpyAsync(E.h_arena, E.arena.p, ARENA_RB, hipMemcpyDeviceToHost, E.stream));
   CCRDT_HIP(hipMemcpyAsync(static_cast<char*>(E.h_arena) + 2 * ARENA_RB, a.lay_cnt, 16 * TRMV_NSUB,
                            hipMemcpyDeviceToHost, E.stream));
   CCRDT_HIP(hipStreamSynchronize(E.stream));
-  const uint32_t* hs = (const uint32_t*)E.h_status;
-  if (hs[3 + 2 * 3]) return trmv_err_code(hs[3 + 2 * 3]);
-  {
-    // the arena's use: what this pass took, what is left; the next batch
-    // runs in place only while the room left covers twice this pass's take
-    const uint64_t(*cnt)[3] = reinterpret_cast<const uint64_t(*)[3]>(E.h_arena);
-    bool roomy = true;
-    for (int x = 0; x < 3; ++x) {
-      uint64_t used = 0, room = 0;
-      for (int i = 0; i < TRMV_NSUB; ++i) {
-        const uint64_t c = std::min(cnt[i][x], E.arena_sub[1][i][x]);
-        used += c - E.arena_sub[0][i][x];
-        room += E.arena_sub[1][i][x] - c;
-      }
-      const uint64_t take = used - std::min(used, E.arena_used[x]);
-      E.arena_used[x] = used;
-      E.arena_rate[x] = std::max(E.arena_rate[x], take);
-      roomy &= room >= 2 * take;
-    }
-    E.inplace_ready = roomy;
-    // keys by layout (ccrdt_engine_overflow_keys slots 6, 7, 8: relocated, appended, compacted)
-    const uint32_t* lc = reinterpret_cast<const uint32_t*>(static_cast<const char*>(E.h_arena) + 2 * ARENA_RB);
-    for (int l = 0; l < 3; ++l) {
-      uint32_t n = 0;
-      for (int i = 0; i < TRMV_NSUB; ++i) n += lc[4 * i + l];
-      E.trmv_overflow_keys[6 + l] = n;
-    }
-  }
-  float mv = 0.f, mr = 0.f;
-  CCRDT_HIP(hipEventElapsedTime(&mv, E.evt[0], E.evt[1]));
-  CCRDT_HIP(hipEventElapsedTime(&mr, E.evt[1], E.evt[2]));
-  E.trmv_tier_ms[5] += mv;  // (the validation pass)
-  E.trmv_tier_ms[3] += mr;
-  handed = hs[2 + 2 * 3];
-  E.trmv_overflow_keys[5] = handed;  // (keys the in-place pass left to the full rewrite)
-  (void)D;
+  // (the validation's errors are in tier R's word)
+  const int tier_r = CCRDT_TRMV_TIER_RESIDENT;
+  CCRDT_TRY(trmv_book(E, st, &tier_r, 1, e0 + 1));
+  // the count is the keys left to the full rewrite: booked as such, and tier
+  // R's own slot left to the rewrite's tier R (or to the partial commit)
+  E.trmv_overflow_keys[CCRDT_TRMV_SLOT_TO_REWRITE] = std::exchange(E.trmv_overflow_keys[tier_r], 0u);
+  float mv = 0.f;
+  CCRDT_HIP(hipEventElapsedTime(&mv, E.evt[e0], E.evt[e0 + 1]));
+  E.trmv_tier_ms[CCRDT_TRMV_MS_VALIDATE] += mv;
+  trmv_arena_account(E);
   return CCRDT_OK;
 }
 
-// A full rewrite: the capacity scan lays every key out in the other data
-// arrays (with room for in-place growth when tier R can take the keys), then
-// the tier chain.  With a.key_done the keys an in-place pass completed are
-// only copied (no ops).
-int trmv_pass_full(Engine& E, TrmvApplyArgs a, uint64_t n_ops, uint32_t* status, int& first_tier, int& n_over) {
-  const int D = E.n_dc;
+// Sizes of a side for `tot` elements; with room to grow in place, more for
+// the keys later in-place batches relocate (the arena): three passes' worth
+// of the most one pass took so far, a quarter of the totals at least.
+int trmv_grow_side(Engine& E, TrmvBufs& b, const uint64_t tot[3], bool room) {
+  const uint64_t nk = (uint64_t)E.n_keys, D = (uint64_t)E.n_dc;
+  uint64_t t[3];
+  for (int x = 0; x < 3; ++x) t[x] = room ? tot[x] + std::max(tot[x] / 4, 3 * E.arena_rate[x]) : tot[x];
+  CCRDT_TRY(b.pl_id.ensure_grow(t[0] * 8));
+  CCRDT_TRY(b.pl_info.ensure_grow(t[0] * 4));
+  CCRDT_TRY(b.pl_slab.ensure_grow(t[0] * 4));
+  CCRDT_TRY(b.pl_gb.ensure_grow(t[0] * 2));
+  CCRDT_TRY(b.m_score.ensure_grow(t[1] * 8));
+  CCRDT_TRY(b.m_ts.ensure_grow(t[1] * 8));
+  CCRDT_TRY(b.m_dc.ensure_grow(t[1]));
+  CCRDT_TRY(b.r_vc.ensure_grow(t[2] * 8 * D));
+  CCRDT_TRY(b.vc.ensure(nk * 8 * D));
+  return CCRDT_OK;
+}
+
+// A full rewrite, 1: capacities -> segment offsets of the new state (r.tot =
+// its totals) and the new side sized for them.  A fresh batch's offsets are
+// the keys' op offsets: trmv_new_meta, no scan.
+int trmv_layout(TrmvRun& r) {
+  Engine& E = r.E;
+  TrmvApplyArgs& a = r.a;
   const uint64_t nk = (uint64_t)E.n_keys;
   const int out = 1 - E.cur, mout = 1 - E.mcur;
-  a.inplace = 0;
-  a.fresh = E.fresh ? 1 : 0;
-  // CCRDT_TRMV_FAIL_FINISH=1 (tests): the full rewrite that finishes an
-  // in-place batch fails as an allocation would (CCRDT_EPARTIAL's path)
-  if (a.key_done) {
-    const char* ff = getenv("CCRDT_TRMV_FAIL_FINISH");
-    if (ff && ff[0] == '1') {
-      set_error("trmv_apply: injected failure of the finishing pass (CCRDT_TRMV_FAIL_FINISH)");
-      return CCRDT_ENOMEM;
-    }
-  }
   // room for in-place growth when tier R can take the keys (K <= 128): the
   // capacity scan's slack, or a fresh batch's roomy layout while its offsets
   // fit 32 bits
-  a.slack = E.k <= 128 ? trmv_pool_slack() : 0;
+  a.slack = E.k <= 128 ? TrmvKnobs::get().pool_slack : 0;
   if (E.fresh && !E.fresh_room) a.slack = 0;  // (ccrdt_trmv_set_fresh_room)
   if (E.fresh && a.slack)
     for (int x = 0; x < 3; ++x)
-      if (trmv_fresh_off(true, x, nk, n_ops) >= 0xFFFFFFFFull) a.slack = 0;
+      if (trmv_fresh_off(true, x, nk, r.n_ops) >= 0xFFFFFFFFull) a.slack = 0;
   a.old_s = E.trmv_side(E.mcur, E.cur);
   CCRDT_TRY(E.trmv[mout].meta.ensure(nk * sizeof(KeyMeta)));
   CCRDT_TRY(E.trmv[mout].cap.ensure(nk * sizeof(KeyCap)));
@@ -449,10 +583,7 @@ int trmv_pass_full(Engine& E, TrmvApplyArgs a, uint64_t n_ops, uint32_t* status,
   const uint64_t nb = (nk + 1023) / 1024;
   // partials: per-tile sums and totals, then each key's rmv-op count (u32)
   CCRDT_TRY(E.partials.ensure((nb * 3 + 3) * sizeof(uint64_t) + nk * sizeof(uint32_t)));
-  // 1) capacities -> segment offsets of the new state (a fresh batch's
-  //    offsets are the keys' op offsets: trmv_new_meta, no scan)
-  uint64_t tot[3];
-  for (int x = 0; x < 3; ++x) tot[x] = trmv_fresh_off(a.slack != 0, x, nk, n_ops);  // (fresh: no scan)
+  for (int x = 0; x < 3; ++x) r.tot[x] = trmv_fresh_off(a.slack != 0, x, nk, r.n_ops);  // (fresh: no scan)
   if (!E.fresh && nk) {
     CCRDT_TRY(trmv_launch_scan(a, E.partials.as<uint64_t>(),
                                reinterpret_cast<uint32_t*>(E.partials.as<uint64_t>() + nb * 3 + 3), E.stream));
@@ -460,291 +591,262 @@ int trmv_pass_full(Engine& E, TrmvApplyArgs a, uint64_t n_ops, uint32_t* status,
     CCRDT_HIP(hipMemcpyAsync(E.h_status, E.partials.as<uint64_t>() + nb * 3, 3 * sizeof(uint64_t),
                              hipMemcpyDeviceToHost, E.stream));
     CCRDT_HIP(hipStreamSynchronize(E.stream));
-    memcpy(tot, E.h_status, sizeof(tot));
+    memcpy(r.tot, E.h_status, sizeof(r.tot));
   }
-  if (tot[0] >= 0xFFFFFFFFull || tot[1] >= 0xFFFFFFFFull || tot[2] >= 0xFFFFFFFFull) {
+  if (r.tot[0] >= 0xFFFFFFFFull || r.tot[1] >= 0xFFFFFFFFull || r.tot[2] >= 0xFFFFFFFFull) {
     set_error("trmv_apply: resident state would exceed 2^32 elements");
     return CCRDT_ENOMEM;
   }
-  // Sizes of the new side: the totals, and with room to grow in place a
-  // quarter more for the keys later batches relocate (the arena)
-  auto grow = [&](TrmvBufs& b, bool room) -> int {
-    // (room: for the keys later in-place batches relocate -- three passes'
-    // worth of the most one pass took so far, a quarter of the totals at least)
-    uint64_t t[3];
-    for (int x = 0; x < 3; ++x) t[x] = room ? tot[x] + std::max(tot[x] / 4, 3 * E.arena_rate[x]) : tot[x];
-    CCRDT_TRY(b.pl_id.ensure_grow(t[0] * 8));
-    CCRDT_TRY(b.pl_info.ensure_grow(t[0] * 4));
-    CCRDT_TRY(b.pl_slab.ensure_grow(t[0] * 4));
-    CCRDT_TRY(b.pl_gb.ensure_grow(t[0] * 2));
-    CCRDT_TRY(b.m_score.ensure_grow(t[1] * 8));
-    CCRDT_TRY(b.m_ts.ensure_grow(t[1] * 8));
-    CCRDT_TRY(b.m_dc.ensure_grow(t[1]));
-    CCRDT_TRY(b.r_vc.ensure_grow(t[2] * 8 * D));
-    CCRDT_TRY(b.vc.ensure(nk * 8 * D));
-    return CCRDT_OK;
-  };
-  CCRDT_TRY(grow(E.trmv[out], a.slack != 0));
+  CCRDT_TRY(trmv_grow_side(E, E.trmv[out], r.tot, a.slack != 0));
   // The current side holds nothing live after reset(): size it too, so the
   // next batch (which writes it) does not allocate.
-  if (E.fresh) CCRDT_TRY(grow(E.trmv[E.cur], false));
+  if (E.fresh) CCRDT_TRY(trmv_grow_side(E, E.trmv[E.cur], r.tot, false));
   a.new_s = E.trmv_side(mout, out);
-  // 2) the chain: its first tier over every key, then each later tier over
-  //    the keys the one before handed on.  Every later tier reads its list
-  //    length from the device, so the whole chain is queued without a host
-  //    round trip; one sync at the end reads the status.
-  // CCRDT_TRMV_FIRST_TIER (tuning knob): -1 = the default chain, 0 = tier 0
-  // first (fresh batches only), 1 = tier S first, 3 = tier R first (resident
-  // batches only).
-  static const int first_env = [] {
-    const char* v = getenv("CCRDT_TRMV_FIRST_TIER");
-    return v ? atoi(v) : -1;
-  }();
-  int chain[4], n_chain = 0;
-  {
-    int first = E.fresh ? 0 : (E.k <= 128 ? 3 : 1);
-    if (first_env == 1 || (first_env == 0 && E.fresh) || (first_env == 3 && !E.fresh && E.k <= 128)) first = first_env;
-    chain[n_chain++] = first;
-    // a fresh batch: tier 0's hand-ons (P > K) go to tier R first, whose
-    // per-key latency is about half of tier S's
-    if (first == 0 && E.k <= 128) chain[n_chain++] = 3;
-    chain[n_chain++] = 1;
-    chain[n_chain++] = 2;
-    if (first == 1) n_chain = 2, chain[1] = 2;
+  return CCRDT_OK;
+}
+
+// A full rewrite, 2: the chain -- its first tier over every key, then each
+// later tier over the keys the one before handed on -- and its head: tier 0
+// and / or tier R, which take every key of the bench streams (a chain that
+// starts at tier S, K > 128, is all head).
+void trmv_plan_chain(TrmvRun& r) {
+  const Engine& E = r.E;
+  const int first_env = TrmvKnobs::get().first_tier;
+  int first = E.fresh ? CCRDT_TRMV_TIER_WAVE : (E.k <= 128 ? CCRDT_TRMV_TIER_RESIDENT : CCRDT_TRMV_TIER_S256);
+  if (first_env == CCRDT_TRMV_TIER_S256 || (first_env == CCRDT_TRMV_TIER_WAVE && E.fresh) ||
+      (first_env == CCRDT_TRMV_TIER_RESIDENT && !E.fresh && E.k <= 128))
+    first = first_env;
+  r.chain[r.n_chain++] = first;
+  // a fresh batch: tier 0's hand-ons (P > K) go to tier R first, whose
+  // per-key latency is about half of tier S's
+  if (first == CCRDT_TRMV_TIER_WAVE && E.k <= 128) r.chain[r.n_chain++] = CCRDT_TRMV_TIER_RESIDENT;
+  r.n_head = r.n_chain;
+  if (first != CCRDT_TRMV_TIER_S256) r.chain[r.n_chain++] = CCRDT_TRMV_TIER_S256;
+  r.chain[r.n_chain++] = CCRDT_TRMV_TIER_S1024;
+  if (first == CCRDT_TRMV_TIER_S256) r.n_head = r.n_chain;
+}
+
+// n tiers queued without a host round trip (every later tier reads its list
+// length from the device; n_host: the first one's, known to the host), then
+// one status read: the tiers' errors, times and hand-on counts.
+int trmv_segment(TrmvRun& r, const int* tiers, int n, uint32_t n_host = 0) {
+  if (!r.E.n_keys) n = 0;
+  const int e0 = r.next_evt;
+  CCRDT_TRY(trmv_mark(r));
+  for (int i = 0; i < n; ++i) CCRDT_TRY(trmv_tier_launch(r, tiers[i], i ? 0 : n_host));
+  CCRDT_HIP(r.st.read_back());
+  return trmv_book(r.E, r.st, tiers, n, e0);
+}
+
+// The overlapped hand-on: a fresh batch's head [tier 0,
+// tier R] with tier R on a second, high-priority stream beside tier 0,
+// taking the keys tier 0 hands on while it runs; tier 0 takes the likely
+// hand-ons (more than min(128, 1.2 pmax) ops) first, so tier R's per-key
+// latency is spent while tier 0 still works instead of after it.  On for
+// engines of at most CCRDT_TRMV_OVERLAP_KEYS keys (default 2^18: a rank of
+// the strong line at N >= 4): the tail it hides is one key's latency, a
+// larger share of a smaller shard's step, and tier 0 runs ~5 % slower beside
+// it (profiles/r06/ab_overlap_waves.txt: 2^17 keys, step 0.404 -> 0.374 ms;
+// 2^20 keys, 2.29 -> 2.34 ms, so off there).
+int trmv_head_overlapped(TrmvRun& r) {
+  Engine& E = r.E;
+  const uint64_t nk = (uint64_t)E.n_keys;
+  if (!E.stream2) {
+    // (created through the priority API at the highest priority: a plain
+    // second stream shared a hardware queue with the engine's and ran after it)
+    int lo = 0, hi = 0;
+    CCRDT_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    CCRDT_HIP(hipStreamCreateWithPriority(&E.stream2, hipStreamNonBlocking, hi));
+    CCRDT_HIP(hipEventCreateWithFlags(&E.ev_ovl, hipEventDisableTiming));
   }
-  first_tier = chain[0];
-  for (int ci = 0; ci < n_chain; ++ci) E.trmv_overflow_keys[chain[ci]] = 0;
-  // The chain's head -- tier 0 and / or tier R, which take every key of the
-  // bench streams -- is queued in one go; its tier S tail only when the
-  // status read after the head says the head handed keys on (a chain that
-  // starts at tier S, K > 128, is all head).  Each segment's kernels read
-  // their list lengths from the device.
-  int n_head = 0;
-  while (n_head < n_chain && (chain[n_head] == 0 || chain[n_head] == 3)) ++n_head;
-  if (n_head == 0) n_head = n_chain;
-  const uint32_t later_grid = (uint32_t)std::min<uint64_t>(nk, TRMV_LATER_GRID);
-  DevBuf* work = nullptr;
-  const uint32_t* n_dev = nullptr;
-  int ev = 0;
-  const uint32_t* hs = (const uint32_t*)E.h_status;
-  // chain[c0, c1): launches, one status read, the tiers' errors, times and hand-on counts
-  auto segment = [&](int c0, int c1) -> int {
-    const int e0 = ev;
-    CCRDT_HIP(hipEventRecord(E.evt[ev++], E.stream));
-    for (int ci = c0; ci < c1 && nk; ++ci) {
-      const int t = chain[ci];
-      DevBuf* ovf = &E.tier_ovf[t];
-      a.key_list = work ? work->as<uint32_t>() : nullptr;
-      a.n_list = work ? 0u : (uint32_t)nk;
-      a.n_list_dev = n_dev;
-      a.ovf_list = ovf->as<uint32_t>();
-      a.status = status + 2 + 2 * t;
-      const uint64_t grid = work ? later_grid : nk;
-      if (t == 0) CCRDT_TRY(trmv_launch_wave(a, grid, E.stream));
-      else if (t == 3) CCRDT_TRY(trmv_launch_resident(a, grid, E.stream));
-      else CCRDT_TRY(trmv_launch_steady(a, t - 1, grid, E.stream));
-      CCRDT_HIP(hipEventRecord(E.evt[ev++], E.stream));
-      work = ovf;
-      n_dev = a.status;
-    }
-    CCRDT_HIP(hipMemcpyAsync(E.h_status, status, TRMV_STATUS_WORDS * 4, hipMemcpyDeviceToHost, E.stream));
-    CCRDT_HIP(hipStreamSynchronize(E.stream));
-    uint32_t err = 0;
-    for (int ci = c0; ci < c1; ++ci) err |= hs[3 + 2 * chain[ci]];
-    if (err) return trmv_err_code(err);
-    for (int ci = c0; ci < c1 && nk; ++ci) {
-      const int t = chain[ci];
-      float ms = 0.f;
-      CCRDT_HIP(hipEventElapsedTime(&ms, E.evt[e0 + ci - c0], E.evt[e0 + ci - c0 + 1]));
-      E.trmv_tier_ms[t] += ms;
-      E.trmv_overflow_keys[t] = hs[2 + 2 * t];
-    }
-    return CCRDT_OK;
-  };
-  // The overlapped hand-on: a fresh batch's head [tier 0,
-  // tier R] with tier R on a second, high-priority stream beside tier 0,
-  // taking the keys tier 0 hands on while it runs; tier 0 takes the likely
-  // hand-ons (more than min(128, 1.2 pmax) ops) first, so tier R's per-key
-  // latency is spent while tier 0 still works instead of after it.  On for
-  // engines of at most CCRDT_TRMV_OVERLAP_KEYS keys (default 2^18: a rank of
-  // the strong line at N >= 4): the tail it hides is one key's latency, a
-  // larger share of a smaller shard's step, and tier 0 runs ~5 % slower beside
-  // it (profiles/r06/ab_overlap_waves.txt: 2^17 keys, step 0.404 -> 0.374 ms;
-  // 2^20 keys, 2.29 -> 2.34 ms, so off there).
-  // CCRDT_TRMV_OVERLAP=0: never; CCRDT_TRMV_OVERLAP_WAVES: tier R's waves
-  // (32: 16 could not keep up with the hand-ons, 48 and 64 slowed tier 0).
-  static const bool overlap_env = [] {
-    const char* v = getenv("CCRDT_TRMV_OVERLAP");
-    return !(v && v[0] == '0');
-  }();
-  static const uint64_t overlap_keys = [] {
-    const char* v = getenv("CCRDT_TRMV_OVERLAP_KEYS");
-    return v ? strtoull(v, nullptr, 10) : (1ull << 18);
-  }();
-  static const uint32_t overlap_waves = [] {
-    const char* v = getenv("CCRDT_TRMV_OVERLAP_WAVES");
-    const int x = v ? atoi(v) : 32;
-    return (uint32_t)(x < 1 ? 1 : (x > 4096 ? 4096 : x));
-  }();
-  auto head_overlapped = [&]() -> int {
-    if (!E.stream2) {
-      // (created through the priority API at the highest priority: a plain
-      // second stream shared a hardware queue with the engine's and ran after it)
-      int lo = 0, hi = 0;
-      CCRDT_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      CCRDT_HIP(hipStreamCreateWithPriority(&E.stream2, hipStreamNonBlocking, hi));
-      CCRDT_HIP(hipEventCreateWithFlags(&E.ev_ovl, hipEventDisableTiming));
-    }
-    // ovl: [done words | claim | first_list count | pad | published hand-ons (key + 1), one per key]
-    constexpr uint32_t O_CLAIM = TRMV_NDONE, O_NFIRST = TRMV_NDONE + 1, O_PUB = TRMV_NDONE + 4;
-    CCRDT_TRY(E.first_list.ensure(nk * 4));
-    CCRDT_TRY(E.ovl.ensure((O_PUB + nk) * 4));
-    uint32_t* ov = E.ovl.as<uint32_t>();
-    CCRDT_HIP(hipMemsetAsync(ov, 0, (O_PUB + nk) * 4, E.stream));
-    const uint32_t pmax = (uint32_t)std::min<int64_t>(E.k, 128);
-    const uint32_t thresh = std::min<uint32_t>(128u, pmax + pmax / 5);
-    CCRDT_TRY(trmv_launch_first_list(a.key_ptr, nk, thresh, E.first_list.as<uint32_t>(), ov + O_NFIRST, E.stream));
-    const int e0 = ev;
-    CCRDT_HIP(hipEventRecord(E.evt[ev++], E.stream));
-    TrmvApplyArgs a0 = a;
-    a0.key_list = nullptr;
-    a0.n_list = (uint32_t)nk;
-    a0.n_list_dev = nullptr;
-    a0.ovf_list = E.tier_ovf[0].as<uint32_t>();
-    a0.status = status + 2;
-    a0.first_list = E.first_list.as<uint32_t>();
-    a0.n_first = ov + O_NFIRST;
-    a0.first_thresh = thresh;
-    a0.pub = ov + O_PUB;
-    a0.n_pub = (uint32_t)nk;
-    a0.done = ov;
-    CCRDT_TRY(trmv_launch_wave(a0, nk, E.stream));
-    CCRDT_HIP(hipEventRecord(E.evt[ev++], E.stream));
-    CCRDT_HIP(hipStreamWaitEvent(E.stream2, E.evt[e0], 0));
-    TrmvApplyArgs a3 = a;
-    a3.key_list = E.tier_ovf[0].as<uint32_t>();
-    a3.n_list = 0;
-    a3.n_list_dev = status + 2;
-    a3.ovf_list = E.tier_ovf[3].as<uint32_t>();
-    a3.status = status + 2 + 2 * 3;
-    a3.pub = ov + O_PUB;
-    a3.n_pub = (uint32_t)nk;
-    a3.done = ov;
-    a3.prod_waves = trmv_wave_waves(nk);
-    a3.claim = ov + O_CLAIM;
-    // CCRDT_TRMV_OVERLAP_STALL=1 (tests): the consumers give up at once when
-    // no hand-on is there yet, and the host's fallback runs
-    const char* stall_env = getenv("CCRDT_TRMV_OVERLAP_STALL");
-    const bool force_stall = stall_env && stall_env[0] == '1';
-    a3.spin_limit = force_stall ? 0u : (1u << 19);  // (~2 s)
-    CCRDT_TRY(trmv_launch_resident_consume(a3, overlap_waves, E.stream2));
-    CCRDT_HIP(hipEventRecord(E.ev_ovl, E.stream2));
-    CCRDT_HIP(hipStreamWaitEvent(E.stream, E.ev_ovl, 0));
-    CCRDT_HIP(hipEventRecord(E.evt[ev++], E.stream));
-    CCRDT_HIP(hipMemcpyAsync(E.h_status, status, TRMV_STATUS_WORDS * 4, hipMemcpyDeviceToHost, E.stream));
-    CCRDT_HIP(hipStreamSynchronize(E.stream));
-    if ((hs[3 + 2 * 3] & TRMV_ERR_STALL) || force_stall) {
-      // tier 0 did not run beside the consumers: tier R over the whole list
-      // after it (a fresh key's tier R rewrites the same result)
-      CCRDT_HIP(hipMemsetAsync(status + 2 + 2 * 3, 0, 8, E.stream));
-      a3.pub = nullptr;
-      a3.done = nullptr;
-      CCRDT_TRY(trmv_launch_resident(a3, later_grid, E.stream));
-      CCRDT_HIP(hipEventRecord(E.evt[ev - 1], E.stream));
-      CCRDT_HIP(hipMemcpyAsync(E.h_status, status, TRMV_STATUS_WORDS * 4, hipMemcpyDeviceToHost, E.stream));
-      CCRDT_HIP(hipStreamSynchronize(E.stream));
-      E.trmv_overflow_keys[9] = 1;  // (diagnostic: the stall fallback ran)
-    }
-    const uint32_t err = hs[3] | hs[3 + 2 * 3];
-    if (err) return trmv_err_code(err);
-    float m0 = 0.f, m3 = 0.f;
-    CCRDT_HIP(hipEventElapsedTime(&m0, E.evt[e0], E.evt[e0 + 1]));
-    CCRDT_HIP(hipEventElapsedTime(&m3, E.evt[e0 + 1], E.evt[e0 + 2]));
-    E.trmv_tier_ms[0] += m0;
-    E.trmv_tier_ms[3] += m3;  // (tier R's tail past tier 0: the rest ran beside it)
-    E.trmv_overflow_keys[0] = hs[2];
-    E.trmv_overflow_keys[3] = hs[2 + 2 * 3];
-    work = &E.tier_ovf[3];
-    n_dev = status + 2 + 2 * 3;
-    return CCRDT_OK;
-  };
-  const bool overlap = overlap_env && E.fresh && nk && nk <= overlap_keys && n_head == 2 && chain[0] == 0 &&
-                       chain[1] == 3;
-  if (overlap) CCRDT_TRY(head_overlapped());
-  else CCRDT_TRY(segment(0, n_head));
-  if (n_head < n_chain && nk && hs[2 + 2 * chain[n_head - 1]] != 0) CCRDT_TRY(segment(n_head, n_chain));
-  // Keys past the 1024-player class: tier 4 (HBM scratch), on the host-known
-  // list tier 2 handed on.
-  const uint32_t n_big = nk ? hs[2 + 2 * 2] : 0u;
+  // ovl: [done words | claim | first_list count | pad | published hand-ons (key + 1), one per key]
+  constexpr uint32_t O_CLAIM = TRMV_NDONE, O_NFIRST = TRMV_NDONE + 1, O_PUB = TRMV_NDONE + 4;
+  CCRDT_TRY(E.first_list.ensure(nk * 4));
+  CCRDT_TRY(E.ovl.ensure((O_PUB + nk) * 4));
+  uint32_t* ov = E.ovl.as<uint32_t>();
+  CCRDT_HIP(hipMemsetAsync(ov, 0, (O_PUB + nk) * 4, E.stream));
+  const uint32_t pmax = (uint32_t)std::min<int64_t>(E.k, 128);
+  const uint32_t thresh = std::min<uint32_t>(128u, pmax + pmax / 5);
+  CCRDT_TRY(trmv_launch_first_list(r.a.key_ptr, nk, thresh, E.first_list.as<uint32_t>(), ov + O_NFIRST, E.stream));
+  const int e0 = r.next_evt;
+  CCRDT_TRY(trmv_mark(r));
+  TrmvApplyArgs a0 = r.a;  // (tier 0's; a3, tier R's, starts from the words they share)
+  a0.pub = ov + O_PUB;
+  a0.n_pub = (uint32_t)nk;
+  a0.done = ov;
+  TrmvApplyArgs a3 = a0;
+  trmv_point(E, r.st, a0, CCRDT_TRMV_TIER_WAVE, -1);
+  a0.first_list = E.first_list.as<uint32_t>();
+  a0.n_first = ov + O_NFIRST;
+  a0.first_thresh = thresh;
+  CCRDT_TRY(trmv_launch_wave(a0, nk, E.stream));
+  CCRDT_TRY(trmv_mark(r));
+  CCRDT_HIP(hipStreamWaitEvent(E.stream2, E.evt[e0], 0));
+  trmv_point(E, r.st, a3, CCRDT_TRMV_TIER_RESIDENT, CCRDT_TRMV_TIER_WAVE);
+  a3.prod_waves = trmv_wave_waves(nk);
+  a3.claim = ov + O_CLAIM;
+  const bool force_stall = TrmvHooks::overlap_stall();
+  a3.spin_limit = force_stall ? 0u : (1u << 19);  // (~2 s)
+  CCRDT_TRY(trmv_launch_resident_consume(a3, TrmvKnobs::get().overlap_waves, E.stream2));
+  CCRDT_HIP(hipEventRecord(E.ev_ovl, E.stream2));
+  CCRDT_HIP(hipStreamWaitEvent(E.stream, E.ev_ovl, 0));
+  CCRDT_TRY(trmv_mark(r));
+  CCRDT_HIP(r.st.read_back());
+  if ((r.st.errors(CCRDT_TRMV_TIER_RESIDENT) & TRMV_ERR_STALL) || force_stall) {
+    // tier 0 did not run beside the consumers: tier R over the whole list
+    // after it (a fresh key's tier R rewrites the same result)
+    CCRDT_HIP(r.st.clear_tier(CCRDT_TRMV_TIER_RESIDENT));
+    a3.pub = nullptr;
+    a3.done = nullptr;
+    CCRDT_TRY(trmv_launch_resident(a3, std::min<uint64_t>(nk, TRMV_LATER_GRID), E.stream));
+    --r.next_evt;  // (tier R's interval now ends here)
+    CCRDT_TRY(trmv_mark(r));
+    CCRDT_HIP(r.st.read_back());
+    E.trmv_overflow_keys[CCRDT_TRMV_SLOT_STALL_FALLBACK] = 1;
+  }
+  // (tier R's time is its tail past tier 0: the rest ran beside it)
+  CCRDT_TRY(trmv_book(E, r.st, r.chain, 2, e0));
+  r.prev = CCRDT_TRMV_TIER_RESIDENT;
+  return CCRDT_OK;
+}
+
+// A full rewrite, 3: the head queued in one go, sequential or overlapped;
+// its tier S tail only when the status read after the head says the head
+// handed keys on.
+int trmv_run_chain(TrmvRun& r) {
+  const Engine& E = r.E;
+  const TrmvKnobs& knobs = TrmvKnobs::get();
+  const bool overlap = knobs.overlap && E.fresh && E.n_keys && (uint64_t)E.n_keys <= knobs.overlap_keys &&
+                       r.n_head == 2 && r.chain[0] == CCRDT_TRMV_TIER_WAVE && r.chain[1] == CCRDT_TRMV_TIER_RESIDENT;
+  if (overlap) CCRDT_TRY(trmv_head_overlapped(r));
+  else CCRDT_TRY(trmv_segment(r, r.chain, r.n_head));
+  if (r.n_head < r.n_chain && E.n_keys && r.st.handed(r.chain[r.n_head - 1]) != 0)
+    CCRDT_TRY(trmv_segment(r, r.chain + r.n_head, r.n_chain - r.n_head));
+  return CCRDT_OK;
+}
+
+// A full rewrite, 4: keys past the 1024-player class go to tier 4 (HBM
+// scratch), on the host-known list tier 2 handed on.  Keys over the per-key
+// capacity (tier 4's hand-ons, n_over) keep their old state; every other key
+// commits.
+int trmv_tier4_and_keep(TrmvRun& r, int& n_over) {
+  Engine& E = r.E;
+  const uint32_t n_big = E.n_keys ? r.st.handed(CCRDT_TRMV_TIER_S1024) : 0u;
   if (n_big) {
-    const uint32_t waves = std::min<uint32_t>(n_big, TRMV_HBM_WAVES);
     CCRDT_TRY(E.hbm_scratch.ensure((uint64_t)TRMV_HBM_WAVES * trmv_steady_hbm_bytes(E.k <= 128)));
-    a.key_list = E.tier_ovf[2].as<uint32_t>();
-    a.n_list = n_big;
-    a.n_list_dev = nullptr;
-    a.ovf_list = E.tier_ovf[4].as<uint32_t>();
-    a.status = status + 2 + 2 * 4;
-    CCRDT_HIP(hipEventRecord(E.evt[ev++], E.stream));
-    CCRDT_TRY(trmv_launch_steady_hbm(a, waves, E.hbm_scratch.p, E.stream));
-    CCRDT_HIP(hipEventRecord(E.evt[ev++], E.stream));
-    CCRDT_HIP(hipMemcpyAsync(E.h_status, status, TRMV_STATUS_WORDS * 4, hipMemcpyDeviceToHost, E.stream));
-    CCRDT_HIP(hipStreamSynchronize(E.stream));
-    const uint32_t e4 = hs[3 + 2 * 4];
-    if (e4) return trmv_err_code(e4);
-    float ms = 0.f;
-    CCRDT_HIP(hipEventElapsedTime(&ms, E.evt[ev - 2], E.evt[ev - 1]));
-    E.trmv_tier_ms[4] += ms;
+    const int tier_hbm = CCRDT_TRMV_TIER_HBM;
+    r.prev = CCRDT_TRMV_TIER_S1024;
+    CCRDT_TRY(trmv_segment(r, &tier_hbm, 1, n_big));
   }
-  E.trmv_overflow_keys[4] = n_big ? hs[2 + 2 * 4] : 0u;
-  // Keys over the per-key capacity (tier 4's hand-ons) keep their old state;
-  // every other key commits.
-  n_over = (int)E.trmv_overflow_keys[4];
+  n_over = (int)E.trmv_overflow_keys[CCRDT_TRMV_TIER_HBM];
   if (n_over) {
-    a.key_list = E.tier_ovf[TRMV_TIER_LAST].as<uint32_t>();
-    a.n_list = 0;
-    a.n_list_dev = status + 2 + 2 * TRMV_TIER_LAST;  // (trmv_keep_kernel reads the count here)
-    CCRDT_TRY(trmv_launch_keep(a, std::min<uint32_t>((uint32_t)n_over, TRMV_LATER_GRID), E.stream));
+    r.a.key_list = E.tier_ovf[TRMV_TIER_LAST].as<uint32_t>();
+    r.a.n_list = 0;
+    r.a.n_list_dev = r.st.count(TRMV_TIER_LAST);  // (trmv_keep_kernel reads the count here)
+    CCRDT_TRY(trmv_launch_keep(r.a, std::min<uint32_t>((uint32_t)n_over, TRMV_LATER_GRID), E.stream));
   }
-  // the arena of the new data arrays (only when in-place batches may
-  // follow: tier 0 / tier R wrote the keys with room): its top = the
-  // layout's totals, its free space cut into TRMV_NSUB sub-arenas.  The
-  // device copy of the table is made by the next in-place pass (arena_pending),
-  // so a fresh batch that no resident batch follows pays no round trip for it.
+  return CCRDT_OK;
+}
+
+// A full rewrite, 5: the arena of the new data arrays (only when in-place
+// batches may follow: tier 0 / tier R wrote the keys with room): its top =
+// the layout's totals, its free space cut into TRMV_NSUB sub-arenas.  The
+// device copy of the table is made by the next in-place pass (arena_pending),
+// so a fresh batch that no resident batch follows pays no round trip for it.
+int trmv_open_arena(TrmvRun& r) {
+  Engine& E = r.E;
+  const uint64_t* tot = r.tot;
+  trmv_side_caps(E, 1 - E.cur, E.arena_cap);
+  if (const char* v = TrmvHooks::arena_room())
+    for (int x = 0; x < 3; ++x) E.arena_cap[x] = std::min<uint64_t>(E.arena_cap[x], tot[x] + strtoull(v, nullptr, 10));
+  auto& sub = E.arena_sub;
+  for (int x = 0; x < 3; ++x) {
+    const uint64_t room = E.arena_cap[x] > tot[x] ? E.arena_cap[x] - tot[x] : 0;
+    for (int i = 0; i < TRMV_NSUB; ++i) {
+      sub[0][i][x] = tot[x] + room * i / TRMV_NSUB;
+      sub[1][i][x] = tot[x] + room * (i + 1) / TRMV_NSUB;
+    }
+    E.arena_used[x] = 0;
+  }
+  CCRDT_TRY(E.arena.ensure(sizeof(sub) + 16 * TRMV_NSUB));
+  E.arena_pending = true;
+  // what the next (in-place) pass writes and reads back, allocated now: its
+  // first use made the first in-place batch after a fresh one 2.4 ms slower
+  // in wall time than its kernels (meta / cap of the other side, 48 B per
+  // key, and the pinned read-back)
+  CCRDT_TRY(E.trmv[E.mcur].meta.ensure((uint64_t)E.n_keys * sizeof(KeyMeta)));
+  CCRDT_TRY(E.trmv[E.mcur].cap.ensure((uint64_t)E.n_keys * sizeof(KeyCap)));
+  (void)trmv_pin_arena(E);  // (else the in-place pass allocates it, or fails cleanly)
+  return CCRDT_OK;
+}
+
+// A full rewrite: the capacity scan lays every key out in the other data
+// arrays (with room for in-place growth when tier R can take the keys), then
+// the tier chain.  With a.key_done the keys an in-place pass completed are
+// only copied (no ops).
+int trmv_pass_full(Engine& E, const TrmvApplyArgs& a, uint64_t n_ops, const TrmvStatus& st, int& first_tier,
+                   int& n_over) {
+  if (a.key_done && TrmvHooks::fail_finish()) {
+    set_error("trmv_apply: injected failure of the finishing pass (CCRDT_TRMV_FAIL_FINISH)");
+    return CCRDT_ENOMEM;
+  }
+  TrmvRun r{E, st, a, n_ops};
+  CCRDT_TRY(trmv_layout(r));
+  trmv_plan_chain(r);
+  first_tier = r.chain[0];
+  CCRDT_TRY(trmv_run_chain(r));
+  CCRDT_TRY(trmv_tier4_and_keep(r, n_over));
   // a fresh roomy layout: no VALID capacity record on a key with a wide add
   // Score (tier 0 writes one for every key it applies; see the kernel)
-  if (E.fresh && a.slack && nk) CCRDT_TRY(trmv_launch_wide_cap(a, nk, E.stream));
-  const bool roomy = a.slack != 0 && (first_tier == 3 || first_tier == 0);
-  if (roomy) {
-    trmv_side_caps(E, out, E.arena_cap);
-    // CCRDT_TRMV_ARENA_ROOM=n (tests): at most n free elements past the top,
-    // so relocations run out and the full rewrite that finishes a batch runs
-    if (const char* v = getenv("CCRDT_TRMV_ARENA_ROOM"))
-      for (int x = 0; x < 3; ++x) E.arena_cap[x] = std::min<uint64_t>(E.arena_cap[x], tot[x] + strtoull(v, nullptr, 10));
-    auto& sub = E.arena_sub;
-    for (int x = 0; x < 3; ++x) {
-      const uint64_t room = E.arena_cap[x] > tot[x] ? E.arena_cap[x] - tot[x] : 0;
-      for (int i = 0; i < TRMV_NSUB; ++i) {
-        sub[0][i][x] = tot[x] + room * i / TRMV_NSUB;
-        sub[1][i][x] = tot[x] + room * (i + 1) / TRMV_NSUB;
-      }
-      E.arena_used[x] = 0;
-    }
-    CCRDT_TRY(E.arena.ensure(sizeof(sub) + 16 * TRMV_NSUB));
-    E.arena_pending = true;
-    // what the next (in-place) pass writes and reads back, allocated now: its
-    // first use made the first in-place batch after a fresh one 2.4 ms slower
-    // in wall time than its kernels (meta / cap of the other side, 48 B per
-    // key, and the pinned read-back)
-    CCRDT_TRY(E.trmv[1 - mout].meta.ensure(nk * sizeof(KeyMeta)));
-    CCRDT_TRY(E.trmv[1 - mout].cap.ensure(nk * sizeof(KeyCap)));
-    if (!E.h_arena && hipHostMalloc(&E.h_arena, 2 * sizeof(E.arena_sub[0]) + 16 * TRMV_NSUB,
-                                    hipHostMallocDefault) != hipSuccess)
-      E.h_arena = nullptr;  // (the in-place pass allocates it, or fails cleanly)
-  }
-  for (int x = 0; x < 3; ++x) E.trmv_tot[out][x] = tot[x];
-  E.cur = out;
-  E.mcur = mout;
+  if (E.fresh && r.a.slack && E.n_keys) CCRDT_TRY(trmv_launch_wide_cap(r.a, (uint64_t)E.n_keys, E.stream));
+  const bool roomy = r.a.slack != 0 && first_tier != CCRDT_TRMV_TIER_S256;  // (tier 0 or tier R wrote the keys)
+  if (roomy) CCRDT_TRY(trmv_open_arena(r));
+  for (int x = 0; x < 3; ++x) E.trmv_tot[1 - E.cur][x] = r.tot[x];
+  E.cur = 1 - E.cur;
+  E.mcur = 1 - E.mcur;
   E.inplace_ready = roomy;
+  return CCRDT_OK;
+}
+
+// The keys an in-place pass handed on: their ops in a full rewrite of every
+// key (the others only copied), which also compacts the arena.  Until it
+// commits, the live state (meta[mcur] over data side cur) is the batch
+// applied to every key but the handed-on ones, which kept theirs; the rewrite
+// writes only the other sides, so when it fails that state stands: a partial
+// commit (partial = CCRDT_EPARTIAL), not a rollback -- the in-place pass
+// already changed the data arrays of the keys it completed.
+int trmv_finish_handed(Engine& E, TrmvApplyArgs a, uint64_t n_ops, const TrmvStatus& st, uint32_t handed,
+                       int& first_tier, int& n_over, int& partial) {
+  const uint64_t nk = (uint64_t)E.n_keys;
+  DevBuf& list = E.tier_ovf[CCRDT_TRMV_TIER_RESIDENT];
+  // (the list, host-side: the rewrite's own tier R overwrites tier_ovf[3])
+  std::vector<uint32_t> hkeys(handed);
+  CCRDT_HIP(hipMemcpy(hkeys.data(), list.p, (size_t)handed * 4, hipMemcpyDeviceToHost));
+  int rc = E.key_done.ensure(nk);
+  if (rc == CCRDT_OK)
+    rc = trmv_launch_mark_done(E.key_done.as<uint8_t>(), nk, list.as<uint32_t>(), handed, nullptr, nullptr, E.stream);
+  if (rc == CCRDT_OK && st.clear() != hipSuccess) rc = CCRDT_EDEVICE;
+  if (rc == CCRDT_OK) {
+    a.key_done = E.key_done.as<uint8_t>();
+    rc = trmv_pass_full(E, a, n_ops, st, first_tier, n_over);
+  }
+  if (rc == CCRDT_OK) return CCRDT_OK;
+  const std::string why = g_last_error;
+  E.inplace_ready = false;  // (the next batch lays every key out again)
+  // the handed-on keys listed again and their extra counts zeroed (a
+  // failed rewrite may have written some): they produce no extras
+  CCRDT_HIP(hipStreamSynchronize(E.stream));  // (whatever the failed rewrite queued)
+  CCRDT_HIP(hipMemcpy(list.p, hkeys.data(), (size_t)handed * 4, hipMemcpyHostToDevice));
+  CCRDT_TRY(trmv_launch_mark_done(E.key_done.as<uint8_t>(), nk, list.as<uint32_t>(), handed, nullptr, a.ex_cnt,
+                                  E.stream));
+  CCRDT_HIP(hipStreamSynchronize(E.stream));
+  E.trmv_overflow_keys[CCRDT_TRMV_TIER_RESIDENT] = handed;
+  set_error("trmv_apply: the batch committed except for " + std::to_string(handed) +
+            " key(s) the in-place pass handed on (ccrdt_engine_handed_on(e, 3)); they keep their previous "
+            "state: the full rewrite that applies their ops failed: " + why);
+  partial = CCRDT_EPARTIAL;
+  first_tier = CCRDT_TRMV_TIER_RESIDENT;
+  n_over = 0;
   return CCRDT_OK;
 }
 
@@ -778,11 +880,10 @@ int ccrdt_trmv_apply_device(ccrdt_engine* e, const ccrdt_trmv_ops* ops) {
   a.rmv_vc = ops->rmv_vc;
   a.n_rmv_rows = ops->rmv_vc ? ops->n_rmv_rows : 0;
   a.fresh = E.fresh ? 1 : 0;
-  // status words: [0..1] scan, [2+2t, 3+2t] tier t (overflow count, errors)
-  CCRDT_TRY(E.status.ensure(TRMV_STATUS_WORDS * 4 + 16));  // (+ the validation's scratch flag)
-  uint32_t* status = E.status.as<uint32_t>();
-  CCRDT_HIP(hipMemsetAsync(E.status.p, 0, TRMV_STATUS_WORDS * 4, E.stream));
-  a.status = status;
+  CCRDT_TRY(E.status.ensure(TrmvStatus::ALLOC));
+  const TrmvStatus st{E.status.as<uint32_t>(), static_cast<uint32_t*>(E.h_status), E.stream};
+  CCRDT_HIP(st.clear());
+  a.status = st.dev;  // (the scan's words)
   CCRDT_TRY(E.ex_cnt.ensure(nk * 4));
   CCRDT_TRY(E.ex.ensure(n_ops * sizeof(TrmvExtraRec)));
   CCRDT_TRY(E.ex_vc.ensure(n_ops * 8 * D));
@@ -797,66 +898,21 @@ int ccrdt_trmv_apply_device(ccrdt_engine* e, const ccrdt_trmv_ops* ops) {
   a.ex_cnt = E.ex_cnt.as<uint32_t>();
   a.ex = E.ex.as<TrmvExtraRec>();
   a.ex_vc = E.ex_vc.as<int64_t>();
-  E.trmv_overflow_keys.clear();
-  E.trmv_tier_ms.clear();
-  // CCRDT_TRMV_INPLACE=0: every resident batch is a full rewrite (A/B knob)
-  static const bool inplace_env = [] {
-    const char* v = getenv("CCRDT_TRMV_INPLACE");
-    return !(v && v[0] == '0');
-  }();
-  int first_tier = 3, n_over = 0;
-  int partial = CCRDT_OK;
-  if (nk && !E.fresh && E.k <= 128 && E.inplace_ready && inplace_env) {
-    uint32_t handed = 0;
-    CCRDT_TRY(trmv_pass_inplace(E, a, n_ops, status, handed));
+  std::fill(std::begin(E.trmv_overflow_keys), std::end(E.trmv_overflow_keys), 0u);
+  std::fill(std::begin(E.trmv_tier_ms), std::end(E.trmv_tier_ms), 0.f);
+  int first_tier = CCRDT_TRMV_TIER_RESIDENT, n_over = 0, partial = CCRDT_OK;
+  if (nk && !E.fresh && E.k <= 128 && E.inplace_ready && TrmvKnobs::get().inplace) {
+    CCRDT_TRY(trmv_pass_inplace(E, a, n_ops, st));
     E.mcur = 1 - E.mcur;  // (meta / cap now hold the batch, except the handed-on keys)
-    if (handed) {
-      // the handed-on keys' ops in a full rewrite of every key (the others
-      // only copied): it also compacts the arena.  Until it commits, the live
-      // state (meta[mcur] over data side cur) is the batch applied to every
-      // key but the handed-on ones, which kept theirs; the rewrite writes only
-      // the other sides, so when it fails that state stands: a partial commit
-      // (CCRDT_EPARTIAL), not a rollback -- the in-place pass already changed
-      // the data arrays of the keys it completed.
-      // (the list, host-side: the rewrite's own tier R overwrites tier_ovf[3])
-      std::vector<uint32_t> hkeys(handed);
-      CCRDT_HIP(hipMemcpy(hkeys.data(), E.tier_ovf[3].p, (size_t)handed * 4, hipMemcpyDeviceToHost));
-      int rc = E.key_done.ensure(nk);
-      if (rc == CCRDT_OK)
-        rc = trmv_launch_mark_done(E.key_done.as<uint8_t>(), nk, E.tier_ovf[3].as<uint32_t>(), handed, nullptr,
-                                   nullptr, E.stream);
-      if (rc == CCRDT_OK && hipMemsetAsync(E.status.p, 0, TRMV_STATUS_WORDS * 4, E.stream) != hipSuccess)
-        rc = CCRDT_EDEVICE;
-      if (rc == CCRDT_OK) {
-        a.key_done = E.key_done.as<uint8_t>();
-        rc = trmv_pass_full(E, a, n_ops, status, first_tier, n_over);
-      }
-      if (rc != CCRDT_OK) {
-        const std::string why = g_last_error;
-        E.inplace_ready = false;  // (the next batch lays every key out again)
-        // the handed-on keys listed again and their extra counts zeroed (a
-        // failed rewrite may have written some): they produce no extras
-        CCRDT_HIP(hipStreamSynchronize(E.stream));  // (whatever the failed rewrite queued)
-        CCRDT_HIP(hipMemcpy(E.tier_ovf[3].p, hkeys.data(), (size_t)handed * 4, hipMemcpyHostToDevice));
-        CCRDT_TRY(trmv_launch_mark_done(E.key_done.as<uint8_t>(), nk, E.tier_ovf[3].as<uint32_t>(), handed, nullptr,
-                                        a.ex_cnt, E.stream));
-        CCRDT_HIP(hipStreamSynchronize(E.stream));
-        E.trmv_overflow_keys[3] = handed;
-        set_error("trmv_apply: the batch committed except for " + std::to_string(handed) +
-                  " key(s) the in-place pass handed on (ccrdt_engine_handed_on(e, 3)); they keep their previous "
-                  "state: the full rewrite that applies their ops failed: " + why);
-        partial = CCRDT_EPARTIAL;
-        first_tier = 3;
-        n_over = 0;
-      }
-    }
+    const uint32_t handed = E.trmv_overflow_keys[CCRDT_TRMV_SLOT_TO_REWRITE];
+    if (handed) CCRDT_TRY(trmv_finish_handed(E, a, n_ops, st, handed, first_tier, n_over, partial));
   } else {
-    CCRDT_TRY(trmv_pass_full(E, a, n_ops, status, first_tier, n_over));
+    CCRDT_TRY(trmv_pass_full(E, a, n_ops, st, first_tier, n_over));
   }
   // the sum of the tiers' own intervals (tier 4 starts after a host round
   // trip, whose gap is not kernel time)
   float kernel_ms = 0.f;
-  for (const auto& tm : E.trmv_tier_ms) kernel_ms += tm.second;
+  for (const float ms : E.trmv_tier_ms) kernel_ms += ms;
   CCRDT_HIP(hipMemcpyAsync(E.ex_key_ptr.p, ops->key_ptr, (nk + 1) * 8, hipMemcpyDeviceToDevice,
                            E.stream));
   E.trmv_first_tier = first_tier;
@@ -1170,16 +1226,12 @@ int ccrdt_trmv_key_sizes(ccrdt_engine* e, uint32_t* np, uint32_t* nm, uint32_t* 
 
 int ccrdt_engine_handed_on(ccrdt_engine* e, int t, uint32_t* keys, int64_t cap, int64_t* n) {
   if (!e || !n || cap < 0) return CCRDT_EINVAL;
-  const int ti = t >= 0 && t < TRMV_N_TIERS ? t : -1;
-  auto it = e->trmv_overflow_keys.find(t);
-  if (ti < 0 || e->type != CCRDT_TOPK_RMV || it == e->trmv_overflow_keys.end()) {
-    *n = 0;
-    return ti < 0 ? CCRDT_EINVAL : CCRDT_OK;
-  }
-  *n = it->second;
+  *n = 0;
+  if (t < 0 || t >= TRMV_N_TIERS) return CCRDT_EINVAL;
+  *n = e->trmv_overflow_keys[t];  // (0 for a tier that did not run, and for the other types)
   const int64_t m = std::min<int64_t>(cap, *n);
   if (m > 0 && keys) {
-    const DevBuf& src = e->tier_ovf[ti];
+    const DevBuf& src = e->tier_ovf[t];
     CCRDT_HIP(hipStreamSynchronize(e->stream));
     CCRDT_HIP(hipMemcpy(keys, src.p, (size_t)m * 4, hipMemcpyDeviceToHost));
   }

@@ -1,7 +1,6 @@
 // engine.hpp — the opaque ccrdt_engine of include/ccrdt.h.
 #pragma once
 #include <cstdint>
-#include <map>
 
 #include "common.hpp"
 #include "trmv_kernels.hpp"
@@ -101,8 +100,9 @@ struct ccrdt_engine {
   int trmv_first_tier = 0;
   uint64_t last_n_ops = 0;
   uint64_t trmv_tot[2][3] = {};  // per side: bound on (players, pool, rows) held
-  std::map<int, uint32_t> trmv_overflow_keys;  // per tier / slot class, last apply
-  std::map<int, float> trmv_tier_ms;
+  // last apply, by CCRDT_TRMV_TIER_* / _SLOT_* / _MS_* (include/ccrdt.h)
+  uint32_t trmv_overflow_keys[CCRDT_TRMV_N_SLOTS] = {};
+  float trmv_tier_ms[CCRDT_TRMV_N_MS] = {};
   // host-API staging
   ccrdt::DevBuf st_kp, st_kind, st_id, st_score, st_dc, st_ts, st_rvc, st_out_kind, st_out_vc;
   void* pin[16] = {};          // pinned upload slots (staging.cpp), allocated on first use

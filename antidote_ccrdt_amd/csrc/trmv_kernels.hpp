@@ -207,6 +207,21 @@ __device__ __forceinline__ KeyMeta trmv_new_meta(const TrmvApplyArgs& a, uint64_
   return a.new_s.meta[k];
 }
 
+// A Removals row (a version clock of up to TRMV_DPAD DCs) in registers, and
+// its entry d (a select chain: no dynamic register index).
+typedef int64_t Row8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ int64_t pick8(const Row8& v, uint32_t d) {
+  int64_t r = v[0];
+#pragma unroll
+  for (int k = 1; k < TRMV_DPAD; ++k) r = d == (uint32_t)k ? v[k] : r;
+  return r;
+}
+
+// gb_sets term order of two elements of one Id: (Score, DcId, Ts).
+__device__ __forceinline__ bool gb_gt(int64_t s1, uint32_t d1, int64_t t1, int64_t s2, uint32_t d2, int64_t t2) {
+  return s1 > s2 || (s1 == s2 && (d1 > d2 || (d1 == d2 && t1 > t2)));
+}
+
 enum : uint32_t {
   TRMV_ERR_KIND = 1u,
   TRMV_ERR_DC = 2u,

@@ -98,14 +98,6 @@ constexpr uint32_t Q_UPG = 64u;  // (inside a merge) an Observed player whose en
 constexpr uint32_t Q_DIRTY = 128u;  // the player's record changes (ops, a moved slab, a promotion): written in P5
 constexpr uint32_t R_DOM = 1u;   // cres: dominated add (:234-237)
 
-__device__ __forceinline__ uint32_t ufl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ int64_t ufl64(int64_t v) {
-  const uint32_t lo = ufl((uint32_t)v), hi = ufl((uint32_t)((uint64_t)v >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ uint32_t perm32(uint32_t v, uint32_t dst) {
-  return (uint32_t)__builtin_amdgcn_ds_permute((int)(dst << 2), (int)v);
-}
 // Lane i <- v of lane i + 1 (lane 63 <- fill): DPP wave_shl:1.
 __device__ __forceinline__ uint32_t wshl1(uint32_t v, uint32_t fill) {
   return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x130, 0xf, 0xf, false);
@@ -126,11 +118,6 @@ __device__ __forceinline__ int64_t mkkey(int64_t score, int64_t id) {
 }
 __device__ __forceinline__ int64_t key_score(int64_t k) { return (int64_t)(int32_t)(uint32_t)((uint64_t)k >> 32); }
 __device__ __forceinline__ int64_t key_id(int64_t k) { return (int64_t)(int32_t)((uint32_t)k ^ 0x80000000u); }
-
-// gb_sets term order of two elements of one Id: (Score, DcId, Ts).
-__device__ __forceinline__ bool gb_gt(int64_t s1, uint32_t d1, int64_t t1, int64_t s2, uint32_t d2, int64_t t2) {
-  return s1 > s2 || (s1 == s2 && (d1 > d2 || (d1 == d2 && t1 > t2)));
-}
 
 // One step of P4's segmented scan over the sorted chunk (DPP: row_shr 1, 2,
 // 4, 8 inside rows of 16, then row_bcast 15 and 31 across rows -- the
@@ -169,46 +156,6 @@ __device__ __forceinline__ void seg_step(int32_t& vs, int64_t& vt, uint32_t& vd,
     }
     vd = (vd & 0x3FFFFFFFu) | ((ok || yok) ? (1u << 30) : 0u) | (yhf ? (1u << 31) : 0u);
   }
-}
-
-// Inclusive max-scan over the wave (DPP row shifts, then row broadcasts):
-// each lane gets the largest value at or below it.
-__device__ __forceinline__ uint32_t wave_incl_max_dpp(uint32_t v) {
-  uint32_t o;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-  v = o > v ? o : v;
-  return v;
-}
-
-typedef int64_t Row8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ int64_t pick8(const Row8& v, uint32_t d) {
-  int64_t r = v[0];
-#pragma unroll
-  for (int k = 1; k < TRMV_DPAD; ++k) r = d == (uint32_t)k ? v[k] : r;
-  return r;
-}
-
-template <int BITS>
-__device__ __forceinline__ uint32_t wave_radix_sort(uint32_t kv) {  // by bits [6, 6 + BITS); payload 6 bits
-#pragma unroll
-  for (int b = 0; b < BITS; ++b) {
-    const bool bit = (kv >> (6 + b)) & 1u;
-    const uint64_t ones = ballot(bit);
-    const uint32_t nz = 64u - (uint32_t)__builtin_popcountll(ones);
-    const uint32_t dst = bit ? nz + mbcnt(ones) : mbcnt(~ones);
-    kv = perm32(kv, dst);
-  }
-  return kv;
 }
 
 // One stable counting pass over a 4-bit digit (bits [6 + SHIFT, 10 + SHIFT))

@@ -194,65 +194,6 @@ __device__ __forceinline__ uint32_t hs_cas(SLds<PCAP, RK>& L, uint32_t h, uint32
   }
 }
 
-__device__ __forceinline__ uint32_t ufl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ int64_t ufl64(int64_t v) {
-  const uint32_t lo = ufl((uint32_t)v), hi = ufl((uint32_t)((uint64_t)v >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// Forward permute: lane i's v goes to lane dst (ds_permute).
-__device__ __forceinline__ uint32_t perm32(uint32_t v, uint32_t dst) {
-  return (uint32_t)__builtin_amdgcn_ds_permute((int)(dst << 2), (int)v);
-}
-
-// Inclusive max-scan over the 64 lanes (DPP; identity 0).
-__device__ __forceinline__ uint32_t wave_incl_max_dpp(uint32_t v) {
-  uint32_t o;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-  v = o > v ? o : v;
-  o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-  v = o > v ? o : v;
-  return v;
-}
-
-// Stable sort of the wave by key bits [6, 6 + BITS) of kv (payload: low 6
-// bits); one ballot split per bit.
-template <int BITS>
-__device__ __forceinline__ uint32_t wave_radix_sort(uint32_t kv) {
-#pragma unroll
-  for (int b = 0; b < BITS; ++b) {
-    const bool bit = (kv >> (6 + b)) & 1u;
-    const uint64_t ones = ballot(bit);
-    const uint32_t nz = 64u - (uint32_t)__builtin_popcountll(ones);
-    const uint32_t dst = bit ? nz + mbcnt(ones) : mbcnt(~ones);
-    kv = perm32(kv, dst);
-  }
-  return kv;
-}
-
-typedef int64_t Row8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ int64_t pick8(const Row8& v, uint32_t d) {
-  int64_t r = v[0];
-#pragma unroll
-  for (int k = 1; k < TRMV_DPAD; ++k) r = d == (uint32_t)k ? v[k] : r;
-  return r;
-}
-
-// gb_sets term order of two elements of one Id: (Score, DcId, Ts).
-__device__ __forceinline__ bool gb_gt(int64_t s1, uint32_t d1, int64_t t1, int64_t s2, uint32_t d2,
-                                      int64_t t2) {
-  return s1 > s2 || (s1 == s2 && (d1 > d2 || (d1 == d2 && t1 > t2)));
-}
-
 template <int PCAP, bool RK>
 __device__ __forceinline__ void s_emit(const TrmvApplyArgs& a, SLds<PCAP, RK>& L, uint64_t op0, uint64_t op,
                                        uint8_t kind, int64_t id, int64_t sc, uint32_t dc, int64_t ts,

@@ -19,6 +19,15 @@ from ._lib import check, lib, ptr
 # The last tier of the topk_rmv chain (the HBM class): its hand-ons are the
 # keys over the per-key capacity (include/ccrdt.h CCRDT_EKEYCAP).
 TRMV_TIER_LAST = 4
+# Mirrors of include/ccrdt.h (tests/test_abi.py compares them): the tiers, the
+# slots of overflow_keys() past the tiers, and tier_ms()'s validation slot.
+TRMV_TIER_WAVE, TRMV_TIER_S256, TRMV_TIER_S1024, TRMV_TIER_RESIDENT, TRMV_TIER_HBM = range(5)
+TRMV_N_TIERS = 5
+TRMV_SLOT_TO_REWRITE, TRMV_SLOT_RELOCATED, TRMV_SLOT_APPENDED, TRMV_SLOT_COMPACTED = 5, 6, 7, 8
+TRMV_SLOT_STALL_FALLBACK = 9
+TRMV_N_SLOTS = 10
+TRMV_MS_VALIDATE = 5
+TRMV_N_MS = 6
 TRMV_MAX_PLAYERS = 16384
 
 
@@ -360,7 +369,7 @@ class TopkRmvEngine(_Engine):
             err.keys, err.extra = self.handed_on(TRMV_TIER_LAST), extra
             raise
         except _lib.PartialCommitError as err:
-            err.keys, err.extra = self.handed_on(3), extra
+            err.keys, err.extra = self.handed_on(TRMV_TIER_RESIDENT), extra
             raise
 
     def extra_count(self) -> int:

@@ -130,13 +130,40 @@ int ccrdt_engine_last_kernel_ms(ccrdt_engine* e, float* ms);
  * 4 = trmv_steady's HBM class (up to CCRDT_TRMV_MAX_PLAYERS players, working
  * set in device scratch).  Chains: fresh 0 -> 3 -> 1 -> 2 (K <= 128),
  * resident 3 -> 1 -> 2;
- * tier 4 runs on tier 2's hand-ons.  Keys handed on by tier `t` in the last
- * batch: */
+ * tier 4 runs on tier 2's hand-ons. */
+#define CCRDT_TRMV_TIER_WAVE 0
+#define CCRDT_TRMV_TIER_S256 1
+#define CCRDT_TRMV_TIER_S1024 2
+#define CCRDT_TRMV_TIER_RESIDENT 3
+#define CCRDT_TRMV_TIER_HBM 4
+#define CCRDT_TRMV_N_TIERS 5
+/* Slots of ccrdt_engine_overflow_keys past the tiers (diagnostics of the last
+ * batch): keys the in-place pass left to the full rewrite that finishes the
+ * batch; keys the in-place pass relocated to the arena / appended to inside
+ * their segments / compacted; 1 when the overlapped hand-on of a fresh batch
+ * stalled and tier 3 ran again over tier 0's whole hand-on list. */
+#define CCRDT_TRMV_SLOT_TO_REWRITE 5
+#define CCRDT_TRMV_SLOT_RELOCATED 6
+#define CCRDT_TRMV_SLOT_APPENDED 7
+#define CCRDT_TRMV_SLOT_COMPACTED 8
+#define CCRDT_TRMV_SLOT_STALL_FALLBACK 9
+#define CCRDT_TRMV_N_SLOTS 10
+/* Slot of ccrdt_engine_tier_ms past the tiers: the in-place pass's validation
+ * of the batch. */
+#define CCRDT_TRMV_MS_VALIDATE 5
+#define CCRDT_TRMV_N_MS 6
+/* Slot `t` of the last topk_rmv batch: the keys tier `t` handed on
+ * (t < CCRDT_TRMV_N_TIERS), or a CCRDT_TRMV_SLOT_* diagnostic.  A slot outside
+ * [0, CCRDT_TRMV_N_SLOTS), or one the batch did not touch, reads 0. */
 int ccrdt_engine_overflow_keys(ccrdt_engine* e, int t, int64_t* n);
-/* Kernel time (HIP events) of tier `t` in the last topk_rmv batch. */
+/* Kernel time (HIP events) of tier `t` in the last topk_rmv batch, or of
+ * CCRDT_TRMV_MS_VALIDATE; 0 outside [0, CCRDT_TRMV_N_MS) and for a tier that
+ * did not run. */
 int ccrdt_engine_tier_ms(ccrdt_engine* e, int t, float* ms);
 /* The keys tier `t` handed on in the last topk_rmv batch (up to `cap` of
- * them into `keys`; *n = how many there were).  Diagnostics / bench. */
+ * them into `keys`; *n = how many there were, 0 for a tier that did not
+ * run).  CCRDT_EINVAL for `t` outside [0, CCRDT_TRMV_N_TIERS).
+ * Diagnostics / bench. */
 int ccrdt_engine_handed_on(ccrdt_engine* e, int t, uint32_t* keys, int64_t cap, int64_t* n);
 
 /* Event timing on the engine stream (for bench.py; HIP events). */

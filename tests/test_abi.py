@@ -35,6 +35,19 @@ def test_library_exports_every_declared_symbol():
     assert decl <= set(_lib.SIGNATURES), sorted(decl - set(_lib.SIGNATURES))
 
 
+def test_trmv_tier_and_slot_names_match_the_header():
+    # the tiers and diagnostic slots include/ccrdt.h names, mirrored in engine.py
+    from antidote_ccrdt_amd import engine
+    txt = open(os.path.join(ROOT, "include", "ccrdt.h")).read()
+    names = dict(re.findall(r"^#define CCRDT_(TRMV_(?:TIER|SLOT|MS|N)_[A-Z0-9_]+) +(\d+)\b", txt, flags=re.M))
+    assert {"TRMV_TIER_WAVE", "TRMV_TIER_HBM", "TRMV_N_TIERS", "TRMV_SLOT_TO_REWRITE", "TRMV_SLOT_STALL_FALLBACK",
+            "TRMV_N_SLOTS", "TRMV_MS_VALIDATE", "TRMV_N_MS"} <= set(names), sorted(names)
+    assert len(names) == 14, sorted(names)
+    for name, value in names.items():
+        assert getattr(engine, name) == int(value), name
+    assert engine.TRMV_TIER_LAST == engine.TRMV_TIER_HBM == engine.TRMV_N_TIERS - 1
+
+
 def test_registry():
     # antidote_ccrdt:is_type/1 and generates_extra_operations/1 (antidote_ccrdt.erl:61-65)
     assert [_lib.lib.ccrdt_is_type(t) for t in range(-1, 7)] == [0, 1, 1, 1, 1, 1, 1, 0]

@@ -219,6 +219,20 @@ def test_empty_batch_and_reset(gpu):
     _compare(eng, orac, b, D, xe, xo)
 
 
+def test_table_edges(gpu):
+    """The per-batch tables (overflow_keys, tier_ms, handed_on) at and past
+    their edges: a slot outside reads 0, a tier outside is EINVAL."""
+    tiny = TopkRmvEngine(4, 4, 8)
+    tiny.apply(gen_trmv(12, 4, 8, seed=3))
+    for s in (-1, 10, 99):
+        assert tiny.overflow_keys(s) == 0 and tiny.tier_ms(s) == 0.0
+    for t in (-1, 5):
+        with pytest.raises(_lib.CcrdtError) as ei:
+            tiny.handed_on(t)
+        assert ei.value.code == _lib.EINVAL
+    assert tiny.handed_on(4).size == 0  # (tier 4 did not run)
+
+
 @pytest.mark.parametrize("room,fresh_room", [(None, False), (0, False), (3000, False), (None, True), (0, True)])
 def test_inplace_stream_arena(gpu, room, fresh_room, monkeypatch):
     """Resident batches updated in place (tier R: appends, slab moves to the
