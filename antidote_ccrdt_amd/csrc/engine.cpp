@@ -314,13 +314,15 @@ int trmv_err_code(uint32_t err) {
 //   CCRDT_TRMV_FIRST_TIER     default -1        -1 = the default chain, 0 = tier 0 first (fresh
 //                                               batches only), 1 = tier S first, 3 = tier R first
 //                                               (resident batches only)
-//   CCRDT_TRMV_OVERLAP        on unless 0       the overlapped hand-on (trmv_head_overlapped)
 //   CCRDT_TRMV_OVERLAP_KEYS   default 2^18      the most keys of an engine that overlaps
 //   CCRDT_TRMV_OVERLAP_WAVES  1..4096, def. 32  tier R's waves beside tier 0 (32: 16 could not keep
 //                                               up with the hand-ons, 48 and 64 slowed tier 0)
 //   CCRDT_TRMV_INPLACE        on unless 0       0: every resident batch is a full rewrite (A/B knob)
 // and the hooks of the tests, read at every call (TrmvHooks: the tests set
 // them inside one process):
+//   CCRDT_TRMV_OVERLAP          on unless 0: the overlapped hand-on (trmv_head_overlapped); a
+//                               hook so that one process can run tier 0's 4-wave build (beside
+//                               the consumers) and its 5-wave build on engines of one size
 //   CCRDT_TRMV_FAIL_FINISH=1    the full rewrite that finishes an in-place batch fails as an
 //                               allocation would (CCRDT_EPARTIAL's path)
 //   CCRDT_TRMV_OVERLAP_STALL=1  the overlapped head's consumers give up at once when no hand-on
@@ -334,7 +336,6 @@ uint64_t env_u64(const char* v, uint64_t dflt) { return v ? strtoull(v, nullptr,
 struct TrmvKnobs {
   int pool_slack = env_int(getenv("CCRDT_TRMV_POOL_SLACK"), 2, 2, 8);
   int first_tier = env_int(getenv("CCRDT_TRMV_FIRST_TIER"), -1, INT32_MIN, INT32_MAX);
-  bool overlap = env_on(getenv("CCRDT_TRMV_OVERLAP"));
   bool inplace = env_on(getenv("CCRDT_TRMV_INPLACE"));
   uint64_t overlap_keys = env_u64(getenv("CCRDT_TRMV_OVERLAP_KEYS"), 1ull << 18);
   uint32_t overlap_waves = (uint32_t)env_int(getenv("CCRDT_TRMV_OVERLAP_WAVES"), 32, 1, 4096);
@@ -345,6 +346,7 @@ struct TrmvKnobs {
 };
 struct TrmvHooks {  // (each one read where it is used, at every call, and only there)
   static bool fail_finish() { return env_is1(getenv("CCRDT_TRMV_FAIL_FINISH")); }
+  static bool overlap() { return env_on(getenv("CCRDT_TRMV_OVERLAP")); }
   static bool overlap_stall() { return env_is1(getenv("CCRDT_TRMV_OVERLAP_STALL")); }
   static const char* arena_room() { return getenv("CCRDT_TRMV_ARENA_ROOM"); }  // (null: not set)
 };
@@ -716,7 +718,7 @@ int trmv_head_overlapped(TrmvRun& r) {
 int trmv_run_chain(TrmvRun& r) {
   const Engine& E = r.E;
   const TrmvKnobs& knobs = TrmvKnobs::get();
-  const bool overlap = knobs.overlap && E.fresh && E.n_keys && (uint64_t)E.n_keys <= knobs.overlap_keys &&
+  const bool overlap = TrmvHooks::overlap() && E.fresh && E.n_keys && (uint64_t)E.n_keys <= knobs.overlap_keys &&
                        r.n_head == 2 && r.chain[0] == CCRDT_TRMV_TIER_WAVE && r.chain[1] == CCRDT_TRMV_TIER_RESIDENT;
   if (overlap) CCRDT_TRY(trmv_head_overlapped(r));
   else CCRDT_TRY(trmv_segment(r, r.chain, r.n_head));

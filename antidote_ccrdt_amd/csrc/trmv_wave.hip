@@ -20,9 +20,26 @@
 //    no claim protocol); players are numbered in hash-slot order (new ones
 //    after the old ones), so the device layout is deterministic;
 //  * scans are DPP (wave_excl_scan_dpp), not LDS-crossbar shuffles;
-//  * each wave runs W_KPW consecutive keys and issues the next key's loads
-//    (bounds, metadata, ops, clocks) before the current key's write-out, so
-//    the first HBM round trip of a key overlaps the previous key's stores;
+//  * each wave runs W_KPW consecutive keys.  A chunk's bounds and metadata
+//    are loaded once (wave_load_chunk).  The next key's ops are issued before
+//    the current key's step 5 and retired by one explicit vmcnt(0) before the
+//    current key's first store; its clock loads are issued right after that
+//    wait, still ahead of the stores.  The wait the compiler puts before
+//    the clocks' first use is a vmcnt(0) (the stores since their issue sit
+//    in loops it cannot count), so it also covers the previous key's stores
+//    and every load issued since: the clocks are therefore written into LDS
+//    only before step 5,
+//    their first use, when both have had steps 1-4 to complete (written
+//    after the hash build, that wait was 7.5 % of a key's time), and the
+//    next key's op loads go out after that wait, never before it;
+//  * addressing: an access into one key's segment is a scalar base (the
+//    key's offset folded in) plus a 32-bit lane offset (at32).  The clock
+//    loads and the chunk header keep 64-bit lane addresses: a row's offset
+//    may pass 32 bits, and the header's keys differ per lane;
+//  * kernel arguments are not held in SGPRs across the kernel (they spilled
+//    to VGPR lanes): the fields a phase uses are read together at its start
+//    through one opaque kernarg pointer (KaOps, KaPool, KaPlayers, ...), so
+//    they merge into wide scalar loads with one wait per phase;
 //  * op elements are stored at their position in player order, so every op
 //    lane reads its player's ops with one LDS round trip each;
 //  * players are decided op-parallel wherever the history allows it (step 5):
@@ -135,6 +152,51 @@ struct alignas(16) WaveLds {
 
 #define KA trmv_kargs()
 
+// Element i of an array whose base is wave-uniform, through a 32-bit byte
+// offset: the access is a scalar base plus a 32-bit lane offset, no 64-bit
+// per-lane address is formed.  Only where i * sizeof(T) < 2^32 (an index
+// inside one key's segment).
+template <class T>
+__device__ __forceinline__ T* at32(T* base, uint32_t i) {
+  using B = typename std::conditional<std::is_const<T>::value, const char, char>::type;
+  return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + (size_t)(uint32_t)(i * (uint32_t)sizeof(T)));
+}
+
+// Adjacent TrmvApplyArgs fields that one phase uses, read together through
+// one kernarg pointer at the start of that phase: the reads merge into one
+// wide scalar load that is waited for once, ahead of the phase's LDS work,
+// and the values live only as long as the phase.
+struct KaOps {  // the op columns
+  const uint8_t* kind;
+  const int64_t* id;
+  const int64_t* score;
+  const uint8_t* dc;
+  const int64_t* ts;
+};
+struct KaPool {  // new side: the Masked pool
+  int64_t* m_score;
+  int64_t* m_ts;
+  uint8_t* m_dc;
+};
+struct KaPlayers {  // new side: the player records
+  int64_t* pl_id;
+  uint32_t* pl_info;
+  uint32_t* pl_slab;
+  uint16_t* pl_gb;
+};
+__device__ __forceinline__ KaOps ka_ops(uint64_t op0) {
+  const auto* ka = KA;
+  return {ka->kind + op0, ka->id + op0, ka->score + op0, ka->dc + op0, ka->ts + op0};
+}
+__device__ __forceinline__ KaPool ka_pool(uint32_t m_off) {
+  const auto* ka = KA;
+  return {ka->new_s.m_score + m_off, ka->new_s.m_ts + m_off, ka->new_s.m_dc + m_off};
+}
+__device__ __forceinline__ KaPlayers ka_players(uint32_t p_off) {
+  const auto* ka = KA;
+  return {ka->new_s.pl_id + p_off, ka->new_s.pl_info + p_off, ka->new_s.pl_slab + p_off, ka->new_s.pl_gb + p_off};
+}
+
 __device__ __forceinline__ uint32_t whash(int64_t id) {
   const uint64_t x = (uint64_t)id * 0x9E3779B97F4A7C15ull;
   return (uint32_t)(x >> 56);  // 8 bits = W_HCAP slots
@@ -188,27 +250,35 @@ struct ChunkHdr {
 
 // Key at work-list position i: the list's entry, or (overlapped hand-on)
 // first_list's entries first and then every key in order.
-__device__ __forceinline__ uint32_t wave_list_key(uint32_t i, uint32_t n_first) {
-  if (KA->first_list) return i < n_first ? KA->first_list[i] : i - n_first;
-  return KA->key_list ? KA->key_list[i] : i;
+__device__ __forceinline__ uint32_t wave_list_key(const uint32_t* first_list, const uint32_t* key_list, uint32_t i,
+                                                 uint32_t n_first) {
+  if (first_list) return i < n_first ? first_list[i] : i - n_first;
+  return key_list ? key_list[i] : i;
 }
 
 __device__ __forceinline__ void wave_load_chunk(const TrmvApplyArgs& a, uint32_t c0, uint32_t n,
                                                 uint32_t n_first, ChunkHdr& h) {
   const int lane = lane_id();
   const uint32_t j = (uint32_t)lane < n ? (uint32_t)lane : 0u;
-  h.key = wave_list_key(c0 + j, n_first);
-  h.lo = KA->key_ptr[h.key];
-  h.hi = KA->key_ptr[h.key + 1];
-  h.skip = KA->first_list ? ballot((uint32_t)lane < n && c0 + j >= n_first && h.hi - h.lo > KA->first_thresh) : 0ull;
+  // read once per chunk, together
+  const auto* ka = KA;
+  const uint64_t* key_ptr = ka->key_ptr;
+  const uint32_t* first_list = ka->first_list;
+  const uint32_t* key_list = ka->key_list;
+  const bool fresh = ka->fresh != 0, room = ka->slack != 0;
+  const uint32_t first_thresh = ka->first_thresh;
+  h.key = wave_list_key(first_list, key_list, c0 + j, n_first);
+  h.lo = key_ptr[h.key];
+  h.hi = key_ptr[h.key + 1];
+  h.skip = first_list ? ballot((uint32_t)lane < n && c0 + j >= n_first && h.hi - h.lo > first_thresh) : 0ull;
 #pragma unroll
   for (int i = 0; i < W_MD; ++i) {
     const uint32_t m = 8 * i + (lane >> 3);
     const uint32_t jm = m < n ? m : 0u;
     const uint32_t km = shfl32(h.key, (int)jm);
-    if (KA->fresh) {  // trmv_new_meta: the fresh layout's offsets, counts 0, Min nil
+    if (fresh) {  // trmv_new_meta: the fresh layout's offsets, counts 0, Min nil
       const uint32_t d = lane & 7;
-      h.meta[i] = d < 3 ? (uint32_t)trmv_fresh_off(KA->slack != 0, (int)d, km, KA->key_ptr[km])
+      h.meta[i] = d < 3 ? (uint32_t)trmv_fresh_off(room, (int)d, km, key_ptr[km])
                         : (d == 7 ? NONE32 : 0u);
     } else {
       h.meta[i] = reinterpret_cast<const uint32_t*>(a.new_s.meta + km)[lane & 7];
@@ -230,32 +300,38 @@ __device__ __forceinline__ void wave_load_key(const TrmvApplyArgs& a, const Chun
       if ((j >> 3) == (uint32_t)i) v = rl32(h.meta[i], (int)(8 * (j & 7) + d));
     m[d] = v;
   }
-  // wave-uniform bases + 32-bit lane offsets (saddr addressing, no 64-bit
-  // per-lane address arithmetic)
-  const int64_t* idp = KA->id + in.op0;
-  const int64_t* scp = KA->score + in.op0;
-  const int64_t* tsp = KA->ts + in.op0;
-  const uint8_t* kp = KA->kind + in.op0;
-  const uint8_t* dp = KA->dc + in.op0;
+  // wave-uniform bases (the key's first op folded in) + 32-bit lane offsets
+  const KaOps o = ka_ops(in.op0);
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const uint32_t l = s * 64 + lane;
-    const bool v = l < in.nops;
-    in.id[s] = v ? LD_IN(idp + l) : 0;
-    in.sc[s] = v ? LD_IN(scp + l) : 0;
-    in.ts[s] = v ? LD_IN(tsp + l) : 0;
-    in.kind[s] = v ? (uint32_t)LD_IN(kp + l) : 0u;
-    in.dc[s] = v ? (uint32_t)LD_IN(dp + l) : 0u;
+    uint32_t l = s * 64 + lane;
+    in.id[s] = in.sc[s] = in.ts[s] = 0;
+    in.kind[s] = in.dc[s] = 0u;
+    if (l < in.nops) {
+      // opaque here: the lane offsets are formed beside the loads, where they
+      // fold into the scalar-base form, instead of once for the whole kernel
+      // as 64-bit VGPR pairs that stay live across every key
+      asm volatile("" : "+v"(l));
+      in.id[s] = LD_IN(at32(o.id, l));
+      in.sc[s] = LD_IN(at32(o.score, l));
+      in.ts[s] = LD_IN(at32(o.ts, l));
+      in.kind[s] = (uint32_t)LD_IN(at32(o.kind, l));
+      in.dc[s] = (uint32_t)LD_IN(at32(o.dc, l));
+    }
   }
 }
 
 // Issue the loads of a key's removal clocks (rmv ops in stream order, 8 lanes
 // per clock row, coalesced) once its ops are in registers; they are consumed
-// after the key's hash build.  A row outside [0, n_rmv_rows) reads row 0: the
+// before the key's step 5.  A row outside [0, n_rmv_rows) reads row 0: the
 // key's validation rejects the batch before any value is used.
 template <class W>
 __device__ __forceinline__ void wave_load_rows(const TrmvApplyArgs& a, W& L, KeyIn& in) {
   const int lane = lane_id();
+  const auto* ka = KA;  // read together, ahead of the ballots and the LDS staging
+  const int64_t* rmv_vc = ka->rmv_vc;
+  const int64_t n_rmv_rows = ka->n_rmv_rows;
+  const uint32_t n_dc = (uint32_t)ka->n_dc;
 #pragma unroll
   for (int s = 0; s < W_RCAP / 8; ++s) in.rv[s] = 0;
   bool r[2];
@@ -265,20 +341,20 @@ __device__ __forceinline__ void wave_load_rows(const TrmvApplyArgs& a, W& L, Key
   const uint64_t b0 = ballot(r[0]), b1 = ballot(r[1]);
   const uint32_t n0 = (uint32_t)__builtin_popcountll(b0);
   const uint32_t n = n0 + (uint32_t)__builtin_popcountll(b1);
-  if (n == 0 || KA->n_rmv_rows <= 0) return;
+  if (n == 0 || n_rmv_rows <= 0) return;
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const uint32_t k = s ? n0 + mbcnt(b1) : mbcnt(b0);
     if (r[s] && k < (uint32_t)W_RCAP)
-      L.rsrc[k] = (in.ts[s] >= 0 && in.ts[s] < KA->n_rmv_rows) ? (uint32_t)in.ts[s] : 0u;
+      L.rsrc[k] = (in.ts[s] >= 0 && in.ts[s] < n_rmv_rows) ? (uint32_t)in.ts[s] : 0u;
   }
   wave_lds_sync();
-  const uint32_t d = (lane & 7) < KA->n_dc ? (lane & 7) : 0u;
+  const uint32_t d = (uint32_t)(lane & 7) < n_dc ? (lane & 7) : 0u;
 #pragma unroll
   for (int s = 0; s < W_RCAP / 8; ++s) {
     const uint32_t k = s * 8 + (lane >> 3);
     const uint32_t row = k < n ? L.rsrc[k] : 0u;
-    in.rv[s] = KA->rmv_vc[(uint64_t)row * KA->n_dc + d];
+    in.rv[s] = rmv_vc[(uint64_t)row * n_dc + d];  // (a row's offset may pass 32 bits: a 64-bit lane address)
   }
   wave_lds_sync();  // rsrc is rewritten for the next key
 }
@@ -296,7 +372,11 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
   // (and spill) across every key
   int lane = lane_id();
   asm volatile("" : "+v"(lane));
-  const int D = KA->n_dc;
+  // scalars of the argument block: read once per key, together
+  const auto* ka0 = KA;
+  const int D = ka0->n_dc;
+  const uint32_t size_k = ka0->k;
+  const int64_t n_rmv_rows = ka0->n_rmv_rows;
 #ifdef TRMV_PROF
   unsigned long long prof_t;
   PROF_STAMP(prof_t);
@@ -317,7 +397,7 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
   } else {
     om = a.old_s.meta[key];
   }
-  const uint32_t pmax = KA->k < (uint32_t)W_PCAP ? KA->k : (uint32_t)W_PCAP;
+  const uint32_t pmax = size_k < (uint32_t)W_PCAP ? size_k : (uint32_t)W_PCAP;
   if (nops > (uint32_t)W_ECAP || om.np > pmax || om.nm + nops > (uint32_t)W_ECAP ||
       om.nr > (uint32_t)W_RCAP)
     return W_NEXT_TIER;
@@ -380,7 +460,7 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
     err |= (xv[s] && xkind[s] > 3) ? TRMV_ERR_KIND : 0u;
     err |= (xa[s] && (int)xdc[s] >= D) ? TRMV_ERR_DC : 0u;
     err |= (xa[s] && xts[s] < 1) ? TRMV_ERR_TS : 0u;
-    err |= (xr[s] && (xts[s] < 0 || xts[s] >= KA->n_rmv_rows)) ? TRMV_ERR_ROW : 0u;
+    err |= (xr[s] && (xts[s] < 0 || xts[s] >= n_rmv_rows)) ? TRMV_ERR_ROW : 0u;
   }
   if (ballot(err != 0)) {
     if (err) atomicOr(&KA->status[1], err);
@@ -435,8 +515,14 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
     }
   }
   PROF_MARK(8);
-  // write the rmv clocks (their loads were issued with the key's ops)
-  {
+  // The rmv clocks (their loads were issued with the key's ops) into LDS
+  // rows [om.nr, om.nr + nrmv); true: a negative entry, the host rejects the
+  // batch (TRMV_ERR_VC).  Called before the rows' first use.
+  auto clock_rows_to_lds = [&]() -> bool {
+#ifdef TRMV_PROF
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), stamped on its own: what the clock-row write waits for
+#endif
+    PROF_MARK(12);
 #pragma unroll
     for (int s = 0; s < W_RCAP / 8; ++s) {
       const uint32_t r = s * 8 + (lane >> 3), d = lane & 7;
@@ -446,10 +532,10 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
     }
     if (ballot(err != 0)) {
       if (err) atomicOr(&KA->status[1], err);
-      return W_REJECT;
+      return true;
     }
-  }
-  PROF_MARK(9);
+    return false;
+  };
   // old players keep their index
   if (!FRESH) {
 #pragma unroll
@@ -493,12 +579,6 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
     if (n3) PSLOT(i3) = (uint8_t)(lane * 4 + 3);
   }
   wave_lds_sync();
-  // the next key's op loads go out here, after the last early return: they
-  // land during steps 4-5; the explicit wait before this key's stores
-  // retires them, so the next key never waits on (and its vmcnt never
-  // counts) this key's stores.  (Non-FRESH keys keep more registers live
-  // through step 4: their next key's loads go out at step 5.)
-  if (FRESH && has_next) wave_load_key(a, hdr, nj, nxt);
 
   PROF_MARK(2);
   // ---- 4. player of every op, Vc, op elements in player order
@@ -616,7 +696,16 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
   wave_lds_sync();
 
   PROF_MARK(3);
-  if (!FRESH && has_next) wave_load_key(a, hdr, nj, nxt);
+  // the rmv clocks go into LDS here, before their first use (steps 5 / 5b),
+  // with their TRMV_ERR_VC check: their loads had steps 1-4 to land, and so
+  // had the previous key's stores that the wait also covers
+  if (clock_rows_to_lds()) return W_REJECT;
+  wave_lds_sync();
+  PROF_MARK(9);
+  // The next key's op loads go out here, after the last early return and
+  // after the wait above, so that wait never covers them: they land during
+  // step 5, and the explicit wait before this key's stores retires them.
+  if (has_next) wave_load_key(a, hdr, nj, nxt);
   if (!FRESH) {
     // ---- 5a. players without rmv or old state, op-parallel: each add
     // decides whether it is its player's Obs[Id] and whether its Ts rises
@@ -703,6 +792,8 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
       // instructions per flag per position)
       const uint64_t Mya = ballot(ya);
       uint64_t Mfb = 0, Mbeaten = 0, Mrisk = 0, Mseen = 0, Mfirst = ~0ull, Mgbeaten = 0, Mgtie = 0;
+      // (walking only the player's other positions, y = x + (x >= me), one
+      // pass fewer, measured slower: 2.132 against 2.078 ms per step)
       const uint32_t p0 = c ? st : (uint32_t)ESINK;
       int64_t sxn = L.esc[p0], txn = L.ets[p0];
       uint32_t kxn = L.ekd[p0];
@@ -780,6 +871,7 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
   // The next key's ops are retired before this key's first store, so the
   // next key never waits on (and its vmcnt never counts) these stores.
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+  PROF_MARK(15);
   // the next key's clock loads go out before this key's first store: a
   // load's data waits for every older vector-memory op, stores included
   if (FRESH && has_next) wave_load_rows(a, L, nxt);
@@ -801,6 +893,7 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
     // included (writing only the surviving positions measured slower: the
     // per-element lookup costs more than the bytes it saves, A/B r04);
     // replayed players' positions are rewritten below
+    const KaPool pool = ka_pool(nmeta.m_off);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const uint32_t q = s * 64 + lane;
@@ -808,9 +901,9 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
       const int64_t sc = L.esc[qq], ts = L.ets[qq];
       const uint32_t kd = L.ekd[qq];
       if (q < nops) {
-        ST_OUT((KA->new_s.m_score + nmeta.m_off) + (q), sc);
-        ST_OUT((KA->new_s.m_ts + nmeta.m_off) + (q), ts);
-        ST_OUT((KA->new_s.m_dc + nmeta.m_off) + (q), (uint8_t)((kd >> 2) & 7u));
+        ST_OUT(at32(pool.m_score, q), sc);
+        ST_OUT(at32(pool.m_ts, q), ts);
+        ST_OUT(at32(pool.m_dc, q), (uint8_t)((kd >> 2) & 7u));
       }
     }
   }
@@ -929,13 +1022,14 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
       // the player's slab at [pstart, pstart + cnt); its record is written
       // with every other player's below
       uint32_t opos = NONE16, gj = 0;
+      const KaPool pool = ka_pool(nmeta.m_off);  // (once per pass, not per element)
       for (uint32_t j = 0; j < cnt; ++j) {
         const uint32_t e2 = L.slab[moff + j];
         const int64_t s2 = L.esc[e2], t2 = L.ets[e2];
         const uint32_t d2 = (L.ekd[e2] >> 2) & 7u;
-        ST_OUT((KA->new_s.m_score + nmeta.m_off) + (st + j), s2);
-        ST_OUT((KA->new_s.m_ts + nmeta.m_off) + (st + j), t2);
-        ST_OUT((KA->new_s.m_dc + nmeta.m_off) + (st + j), (uint8_t)d2);
+        ST_OUT(at32(pool.m_score, st + j), s2);
+        ST_OUT(at32(pool.m_ts, st + j), t2);
+        ST_OUT(at32(pool.m_dc, st + j), (uint8_t)d2);
         opos = e2 == o ? j : opos;
         // gb_sets:largest so far (re-read from LDS: no registers held across)
         const uint32_t eb = L.slab[moff + gj];
@@ -969,6 +1063,7 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
     // slab of a decided player: its last segment (every op if it has no
     // rmv); of a replayed player: [pstart, pstart + final count)
     uint32_t csum = 0;
+    const KaPlayers rec = ka_players(nmeta.p_off);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const uint32_t p = s * 64 + lane;
@@ -990,11 +1085,10 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
       // segment, strictly rising Ts, so no two elements tie) or 5b (replayed)
       const uint32_t gb = (replayed || cnt > 1) ? ((wb >> 16) & 0xFFu) - off : 0u;
       if (act) {
-        ST_OUT((KA->new_s.pl_id + nmeta.p_off) + (p), id);
-        ST_OUT((KA->new_s.pl_slab + nmeta.p_off) + (p), off | (cnt << 16));
-        if (cnt > 1) ST_OUT((KA->new_s.pl_gb + nmeta.p_off) + (p), (uint16_t)gb);  // readers take 0 for cnt <= 1
-        ST_OUT(KA->new_s.pl_info + nmeta.p_off + p, (o == NONE8 ? NONE16 : o - off) |
-                                             ((prow != NONE8 ? rix : NONE16) << 16));
+        ST_OUT(at32(rec.pl_id, p), id);
+        ST_OUT(at32(rec.pl_slab, p), off | (cnt << 16));
+        ST_OUT(at32(rec.pl_info, p), (o == NONE8 ? NONE16 : o - off) | ((prow != NONE8 ? rix : NONE16) << 16));
+        if (cnt > 1) ST_OUT(at32(rec.pl_gb, p), (uint16_t)gb);  // readers take 0 for cnt <= 1
       }
       csum += cnt;
       nobs += (uint32_t)__builtin_popcountll(ballot(o != NONE8));
@@ -1084,14 +1178,31 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
   }
   }  // !FRESH
   PROF_MARK(10);
+#ifdef TRMV_PROF
+  {  // one kernarg read and its wait, as the real build has them at each use; then the stamps' own cost
+    unsigned long long probe;
+    asm volatile("s_load_dwordx2 %0, %1, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=s"(probe) : "s"(KA) : "memory");
+    asm volatile("" ::"s"(probe));
+  }
+  PROF_MARK(13);
+  PROF_MARK(14);
+#endif
   // Removals rows (8 lanes per row), Vc, Min, metadata
+  const auto* ka1 = KA;  // r_vc and vc are adjacent: read together, once (not per pass of the loop)
+  int64_t* const rvc = ka1->new_s.r_vc + (uint64_t)nmeta.r_off * D;
+  int64_t* const kvc = ka1->new_s.vc + (uint64_t)key * D;
   for (uint32_t r0 = 0; r0 < rbase; r0 += 8) {
     const uint32_t r = r0 + (lane >> 3), d = lane & 7;
     const int64_t v = L.rows[L.rl[r < rbase ? r : 0u]][d];
-    if (r < rbase && (int)d < D) (KA->new_s.r_vc + (uint64_t)nmeta.r_off * D)[r * D + d] = v;
+    if (r < rbase && (int)d < D) *at32(rvc, r * D + d) = v;
   }
-  if (lane < D) KA->new_s.vc[(uint64_t)key * D + lane] = (int64_t)L.vc[lane];
+  if (lane < D) *at32(kvc, (uint32_t)lane) = (int64_t)L.vc[lane];
   PROF_MARK(11);
+  const auto* ka2 = KA;  // what the key's last stores need, read together, ahead of the Min reduction
+  KeyMeta* const meta_out = ka2->new_s.meta + key;
+  KeyCap* const cap_out = ka2->new_s.cap + key;
+  uint32_t* const ex_cnt_out = ka2->ex_cnt + key;
+  const bool room = ka2->slack != 0;
   // Min = min_observed(Observed) by (Score, Id) — Ids are distinct (:398-406)
   {
     if (!FRESH) {
@@ -1132,16 +1243,16 @@ __device__ __forceinline__ int trmv_wave_key(const TrmvApplyArgs& a, uint32_t ke
     out.nr = rbase;
     out.nobs = nobs;
     out.minq = best_q;
-    KA->new_s.meta[key] = out;
-    KA->ex_cnt[key] = L.nex;
-    if (FRESH && KA->slack) {  // the fresh layout's room: later batches grow the key in place
+    *meta_out = out;
+    *ex_cnt_out = L.nex;
+    if (FRESH && room) {  // the fresh layout's room: later batches grow the key in place
       KeyCap c;
       c.p_cap = trmv_fresh_cap(true, 0, nops);
       c.m_cap = trmv_fresh_cap(true, 1, nops);
       c.r_cap = trmv_fresh_cap(true, 2, nops);
       c.m_top = (uint16_t)nops;  // (every slab lies in the key's op positions)
       c.flags = TRMV_CAP_VALID;
-      KA->new_s.cap[key] = c;
+      *cap_out = c;
     }
   }
   PROF_MARK(5);

@@ -15,12 +15,16 @@ sys.path.insert(0, ROOT)
 from antidote_ccrdt_amd import _lib  # noqa: E402
 from antidote_ccrdt_amd.engine import DeviceTrmvBatch, TopkRmvEngine, gen_trmv  # noqa: E402
 
-NAMES = ["loads issue + LDS init", "validate + rmv rank", "hash + clocks + numbering",
-         "player/op + counting sort", "pool write + replayed players (5b)",
-         "records + rows/min/meta", "step 5: players decided op-parallel",
-         "wait next key's ops + issue its clock loads",
-         "hash build (CAS loop) [split of 2]", "clock rows into LDS (waits their loads) [split of 2]",
-         "records pass [split of 5]", "rows + Vc stores [split of 5]"]
+# (index = the mark's number in trmv_wave.hip; every mark closes its own interval)
+NAMES = ["loads issue + LDS init", "validate + rmv rank", "old players + numbering (after the hash build)",
+         "step 4: player/op + counting sort", "pool write + replayed players (5b)",
+         "Min + metadata", "next key's op loads issued + step 5: players decided op-parallel",
+         "issue of the next key's clock loads",
+         "hash build (CAS loop)", "clock rows into LDS (after step 4)",
+         "records pass", "rows + Vc stores",
+         "vmcnt(0) before the clock-row write (after step 4)",
+         "probe: one kernarg read + its wait (+ a stamp)", "probe: a stamp alone",
+         "pack replayed players + wait next key's ops"]
 n_ops = int(os.environ.get("N_OPS", 100_000_000))
 b = gen_trmv(n_ops, 1 << 20, 8, n_players=256, score_max=10**6, rmv_pm=100, lag_max=64)
 db = DeviceTrmvBatch(b)
