@@ -176,6 +176,7 @@ SIGNATURES = {
     "ccrdt_wc_apply_device": (INT, [P, C.POINTER(WcDocs)]),
     "ccrdt_wc_sizes": (INT, [P, C.POINTER(I64), C.POINTER(I64)]),
     "ccrdt_wc_last_checks": (INT, [P, C.POINTER(I64)]),
+    "ccrdt_wc_last_route": (INT, [P, C.POINTER(I64)]),
     "ccrdt_wc_export": (INT, [P, P, P, P, P]),
     "ccrdt_lb_extras_device": (INT, [P, P, I64, P]),
     "ccrdt_lb_value_size": (INT, [P, I64, P, C.POINTER(I64)]),

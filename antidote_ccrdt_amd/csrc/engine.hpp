@@ -37,6 +37,7 @@ struct TypeBufs {
   uint64_t arena_cap = 0;
   uint64_t wc_seed = 0;   // word-hash seed; a batch that meets a collision is re-run once with a new one
   int64_t wc_checks = 0;  // the last batch's check-list records (-1: verified token by token)
+  int64_t wc_route[CCRDT_WC_N_ROUTE] = {};  // the last batch's route (CCRDT_WC_ROUTE_*)
   // scratch shared by the types
   DevBuf caps, part, ovf_a, ovf_b, status, ex_cnt, ex, kp, stage[8];
   // HBM class of topk / leaderboard (keys beyond the LDS classes)

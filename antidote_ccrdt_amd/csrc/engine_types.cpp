@@ -30,16 +30,6 @@ static int h2d(Engine& E, DevBuf& d, const void* src, uint64_t bytes) {
 }
 
 template <class T>
-static int d2h(std::vector<T>& v, const DevBuf& d, uint64_t n, hipStream_t st) {
-  v.resize(n);
-  if (n) {
-    CCRDT_HIP(hipMemcpyAsync(v.data(), d.p, n * sizeof(T), hipMemcpyDeviceToHost, st));
-    CCRDT_HIP(hipStreamSynchronize(st));
-  }
-  return CCRDT_OK;
-}
-
-template <class T>
 static int d2h_at(std::vector<T>& v, const DevBuf& d, uint64_t at, uint64_t n, hipStream_t st) {
   v.resize(n);
   if (n) {
@@ -47,6 +37,11 @@ static int d2h_at(std::vector<T>& v, const DevBuf& d, uint64_t at, uint64_t n, h
     CCRDT_HIP(hipStreamSynchronize(st));
   }
   return CCRDT_OK;
+}
+
+template <class T>
+static int d2h(std::vector<T>& v, const DevBuf& d, uint64_t n, hipStream_t st) {
+  return d2h_at(v, d, 0, n, st);
 }
 
 // CSR splice: keys [k0, k1) of (fp, fv...) replaced by the range image (ip, iv...).
@@ -110,15 +105,9 @@ int ccrdt_engine::clone_from(const ccrdt_engine& src) {
     CCRDT_TRY(copy_buf(trmv[mcur].cap, src.trmv[src.mcur].cap, stream));
     CCRDT_TRY(copy_buf(arena, src.arena, stream));
     CCRDT_TRY(copy_buf(obs_ord, src.obs_ord, stream));
-    CCRDT_TRY(copy_buf(d.pl_id, s.pl_id, stream));
-    CCRDT_TRY(copy_buf(d.pl_info, s.pl_info, stream));
-    CCRDT_TRY(copy_buf(d.pl_slab, s.pl_slab, stream));
-    CCRDT_TRY(copy_buf(d.pl_gb, s.pl_gb, stream));
-    CCRDT_TRY(copy_buf(d.m_score, s.m_score, stream));
-    CCRDT_TRY(copy_buf(d.m_ts, s.m_ts, stream));
-    CCRDT_TRY(copy_buf(d.m_dc, s.m_dc, stream));
-    CCRDT_TRY(copy_buf(d.r_vc, s.r_vc, stream));
-    CCRDT_TRY(copy_buf(d.vc, s.vc, stream));
+    for (auto m : {&TrmvBufs::pl_id, &TrmvBufs::pl_info, &TrmvBufs::pl_slab, &TrmvBufs::pl_gb, &TrmvBufs::m_score,
+                   &TrmvBufs::m_ts, &TrmvBufs::m_dc, &TrmvBufs::r_vc, &TrmvBufs::vc})
+      CCRDT_TRY(copy_buf(d.*m, s.*m, stream));
   } else {
     const int c = src.tb.tcur;
     tb.tcur = c;
@@ -170,16 +159,11 @@ static int check_csr(const uint64_t* key_ptr, uint64_t nk, uint64_t n) {
   return CCRDT_OK;
 }
 
-static int read_status(ccrdt_engine* e, uint32_t* out2) {
-  CCRDT_HIP(hipMemcpyAsync(e->h_status, e->tb.status.p, 8, hipMemcpyDeviceToHost, e->stream));
+// The first `words` words of tb.status (at least 64 bytes), after the stream's work.
+static int read_status(ccrdt_engine* e, uint32_t* out, int words = 2) {
+  CCRDT_HIP(hipMemcpyAsync(e->h_status, e->tb.status.p, words * 4, hipMemcpyDeviceToHost, e->stream));
   CCRDT_HIP(hipStreamSynchronize(e->stream));
-  memcpy(out2, e->h_status, 8);
-  return CCRDT_OK;
-}
-static int read_status3(ccrdt_engine* e, uint32_t* out3) {
-  CCRDT_HIP(hipMemcpyAsync(e->h_status, e->tb.status.p, 12, hipMemcpyDeviceToHost, e->stream));
-  CCRDT_HIP(hipStreamSynchronize(e->stream));
-  memcpy(out3, e->h_status, 12);
+  memcpy(out, e->h_status, words * 4);
   return CCRDT_OK;
 }
 
@@ -228,6 +212,97 @@ static int hbm_regions(ccrdt_engine* e, const uint32_t* list, uint64_t n, const 
   *total = t;
   return CCRDT_OK;
 }
+
+// The size-class ladder of topk apply, topk value and leaderboard apply: class
+// 0 runs over every key, each later class over the keys the one before listed
+// as too large for it (status word 0 counts them), until none are left.  The
+// lists ping-pong between tb.ovf_a and tb.ovf_b.  Per class: a.key_list /
+// a.ovf_list are set; the last class, the HBM one, gets its regions from
+// hbm(list, n) (hbm_regions and the caller's scratch) as a.tab_off / a.tab_cap;
+// the status pair is cleared, launch(a, cls, n, stream) queues the kernel and the pair is
+// read back (one copy, one sync).  kernel_ms (may be null): the kernels' event
+// time, added up.  word1_error (may be null): the message of CCRDT_EINVAL when
+// a class leaves status word 1 non-zero.
+template <class Args, class Hbm, class Launch>
+static int class_ladder(ccrdt_engine* e, Args& a, int n_classes, float* kernel_ms, const char* word1_error,
+                        Hbm hbm, Launch launch) {
+  TypeBufs& T = e->tb;
+  uint64_t n_work = (uint64_t)e->n_keys;
+  const uint32_t* list = nullptr;
+  for (int cls = 0; cls < n_classes && n_work; ++cls) {
+    uint32_t* ovf = (list == T.ovf_a.as<uint32_t>() ? T.ovf_b : T.ovf_a).as<uint32_t>();
+    a.key_list = list;
+    a.ovf_list = ovf;
+    if (cls == n_classes - 1) {
+      CCRDT_TRY(hbm(list, n_work));
+      a.tab_off = T.hb_off.as<uint64_t>();
+      a.tab_cap = T.hb_cap.as<uint32_t>();
+    }
+    CCRDT_HIP(hipMemsetAsync(T.status.p, 0, 8, e->stream));
+    if (kernel_ms) CCRDT_HIP(hipEventRecord(e->evk0, e->stream));
+    CCRDT_TRY(launch(a, cls, n_work, e->stream));
+    if (kernel_ms) CCRDT_HIP(hipEventRecord(e->evk1, e->stream));
+    uint32_t st[2];
+    CCRDT_TRY(read_status(e, st));
+    if (kernel_ms) {
+      float ms = 0.f;
+      CCRDT_HIP(hipEventElapsedTime(&ms, e->evk0, e->evk1));
+      *kernel_ms += ms;
+    }
+    if (st[1] && word1_error) {
+      set_error(word1_error);
+      return CCRDT_EINVAL;
+    }
+    n_work = st[0];
+    list = ovf;
+  }
+  return CCRDT_OK;
+}
+
+// The environment hooks of this file.  Each is read by the call that uses it,
+// every time (the tests set them between two engines of one process), never
+// once per process.
+//   CCRDT_WC_SLOTS           wc_plan_sizes      slots of the first attempt's word table
+//   CCRDT_WC_CHK_CAP         wc_plan_sizes      capacity of the check list (0: always the verify pass)
+//   CCRDT_WC_NOLIST          wc_plan_sizes      1: device adds, no count list
+//   CCRDT_WC_DLIST           wc_plan_sizes      0: worddocumentcount's dedupe table, no document lists
+//   CCRDT_WC_CL_BLOCKS       wc_plan_sizes      count-list blocks per shard (1: the list fills up)
+//   CCRDT_WC_LAUNCH_TOKENS   wc_plan_sizes      worddocumentcount tokens per insert launch
+//   CCRDT_WC_DTAGS           wc_plan_sizes      document tags before the dedupe table is cleared
+//   CCRDT_WC_DCLEAR          wc_dedupe_table    (diagnostic) the dedupe table cleared at every launch
+//   CCRDT_WC_IDBG            wc_insert_launches (diagnostic) WcArgs::dbg of the insert kernel
+//   CCRDT_WC_VERIFY          wc_persist_and_check  1: every batch verified token by token
+//   CCRDT_WC_WEAK0           wc_table_args      a degenerate word hash under seed 0 (collisions)
+//   CCRDT_WC_PART_MAX_WORDS  ccrdt_wc_partition_device  lowers the row limit of the device exchange
+//   CCRDT_LB_SEQ             ccrdt_lb_apply_device      1: the sequential replay, not the op-parallel boards
+namespace {
+struct WcHooks {  // (dflt: the value when the hook is not set)
+  static uint64_t u64(const char* name, uint64_t dflt) {
+    const char* s = getenv(name);
+    return s ? strtoull(s, nullptr, 0) : dflt;
+  }
+  static int num(const char* name, int dflt) {
+    const char* s = getenv(name);
+    return s ? atoi(s) : dflt;
+  }
+  static uint64_t slots(uint64_t dflt) { return u64("CCRDT_WC_SLOTS", dflt); }
+  static uint64_t chk_cap(uint64_t dflt) { return u64("CCRDT_WC_CHK_CAP", dflt); }
+  static bool no_list() { return num("CCRDT_WC_NOLIST", 0) != 0; }
+  static bool doc_lists() { return num("CCRDT_WC_DLIST", 1) != 0; }
+  static uint64_t cl_blocks(uint64_t dflt) { return u64("CCRDT_WC_CL_BLOCKS", dflt); }
+  static uint64_t launch_tokens(uint64_t dflt) { return u64("CCRDT_WC_LAUNCH_TOKENS", dflt); }
+  static uint64_t dtags(uint64_t dflt) { return u64("CCRDT_WC_DTAGS", dflt); }
+  static bool dclear() { return getenv("CCRDT_WC_DCLEAR") != nullptr; }
+  static int idbg() { return num("CCRDT_WC_IDBG", 0); }
+  static bool verify() { return num("CCRDT_WC_VERIFY", 0) != 0; }
+  static bool weak0() { return getenv("CCRDT_WC_WEAK0") != nullptr; }
+  static uint64_t part_max_words(uint64_t dflt) { return u64("CCRDT_WC_PART_MAX_WORDS", dflt); }
+  static bool lb_seq() {
+    const char* s = getenv("CCRDT_LB_SEQ");
+    return s && s[0] == '1';
+  }
+};
+}  // namespace
 
 extern "C" {
 
@@ -368,36 +443,18 @@ int ccrdt_topk_apply_device(ccrdt_engine* e, const ccrdt_topk_ops* ops) {
   a.score_out = T.tk_score[out].as<int64_t>();
   a.fresh = e->fresh ? 1 : 0;
   a.status = T.status.as<uint32_t>();
-  uint64_t n_work = nk;
-  const uint32_t* list = nullptr;
   float total_ms = 0.f;
-  for (int cls = 0; cls < 4 && n_work; ++cls) {
-    DevBuf* ovf = (list == T.ovf_a.as<uint32_t>()) ? &T.ovf_b : &T.ovf_a;
-    a.key_list = list;
-    a.ovf_list = ovf->as<uint32_t>();
-    if (cls == 3) {  // HBM hash: cap + 1 slots per key
-      uint64_t slots = 0;
-      CCRDT_TRY(hbm_regions(e, list, n_work, ops->key_ptr, e->fresh ? nullptr : a.cnt_in, 1, 2, &slots));
-      slots += n_work;
-      CCRDT_TRY(T.hb_a.ensure(slots * 8));
-      CCRDT_TRY(T.hb_b.ensure(slots * 4));
-      a.tab_off = T.hb_off.as<uint64_t>();
-      a.tab_cap = T.hb_cap.as<uint32_t>();
-      a.g_id = T.hb_a.as<int64_t>();
-      a.g_seq = T.hb_b.as<int32_t>();
-    }
-    CCRDT_HIP(hipMemsetAsync(T.status.p, 0, 8, e->stream));
-    CCRDT_HIP(hipEventRecord(e->evk0, e->stream));
-    CCRDT_TRY(topk_launch_apply(a, cls, n_work, e->stream));
-    CCRDT_HIP(hipEventRecord(e->evk1, e->stream));
-    uint32_t st[2];
-    CCRDT_TRY(read_status(e, st));
-    float ms = 0.f;
-    CCRDT_HIP(hipEventElapsedTime(&ms, e->evk0, e->evk1));
-    total_ms += ms;
-    n_work = st[0];
-    list = ovf->as<uint32_t>();
-  }
+  auto hbm = [&](const uint32_t* list, uint64_t n_work) -> int {  // HBM hash: cap + 1 slots per key
+    uint64_t slots = 0;
+    CCRDT_TRY(hbm_regions(e, list, n_work, ops->key_ptr, e->fresh ? nullptr : a.cnt_in, 1, 2, &slots));
+    slots += n_work;
+    CCRDT_TRY(T.hb_a.ensure(slots * 8));
+    CCRDT_TRY(T.hb_b.ensure(slots * 4));
+    a.g_id = T.hb_a.as<int64_t>();
+    a.g_seq = T.hb_b.as<int32_t>();
+    return CCRDT_OK;
+  };
+  CCRDT_TRY(class_ladder(e, a, 4, &total_ms, nullptr, hbm, topk_launch_apply));
   e->last_kernel_ms = total_ms;
   T.tcur = out;
   e->fresh = false;
@@ -457,16 +514,7 @@ void topk_export_host(const TopkHost& h, uint64_t nk, uint64_t* ptr, int64_t* id
 }  // namespace
 
 int ccrdt_topk_size(ccrdt_engine* e, int64_t* n_entries) {
-  CCRDT_TRY(check_type(e, CCRDT_TOPK));
-  const uint64_t nk = (uint64_t)e->n_keys;
-  int64_t s = 0;
-  if (!e->fresh && nk) {
-    std::vector<uint32_t> cnt;
-    CCRDT_TRY(d2h(cnt, e->tb.tk_cnt[e->tb.tcur], nk, e->stream));
-    for (uint32_t c : cnt) s += c;
-  }
-  *n_entries = s;
-  return CCRDT_OK;
+  return ccrdt_topk_range_size(e, 0, e ? e->n_keys : 0, n_entries);
 }
 
 int ccrdt_topk_export(ccrdt_engine* e, uint64_t* ptr, int64_t* id, int64_t* score) {
@@ -570,29 +618,17 @@ int ccrdt_topk_value(ccrdt_engine* e, uint64_t* ptr, int64_t* id, int64_t* score
   a.out_id = T.stage[2].as<int64_t>();
   a.out_score = T.stage[3].as<int64_t>();
   a.status = T.status.as<uint32_t>();
-  uint64_t n_work = nk;
-  const uint32_t* list = nullptr;
-  for (int cls = 0; cls < 3 && n_work; ++cls) {
-    DevBuf* ovf = (list == T.ovf_a.as<uint32_t>()) ? &T.ovf_b : &T.ovf_a;
-    a.key_list = list;
-    a.ovf_list = ovf->as<uint32_t>();
-    if (cls == 2) {  // HBM bitonic sort regions
-      uint64_t slots = 0;
-      CCRDT_TRY(hbm_regions(e, list, n_work, nullptr, a.cnt, 1, 1, &slots));
-      CCRDT_TRY(T.hb_a.ensure(slots * 8));
-      CCRDT_TRY(T.hb_b.ensure(slots * 8));
-      a.tab_off = T.hb_off.as<uint64_t>();
-      a.tab_cap = T.hb_cap.as<uint32_t>();
-      a.g_id = T.hb_a.as<int64_t>();
-      a.g_score = T.hb_b.as<int64_t>();
-    }
-    CCRDT_HIP(hipMemsetAsync(T.status.p, 0, 8, e->stream));
-    CCRDT_TRY(topk_launch_value(a, cls, n_work, e->stream));
-    uint32_t st[2];
-    CCRDT_TRY(read_status(e, st));
-    n_work = st[0];
-    list = ovf->as<uint32_t>();
-  }
+  auto hbm = [&](const uint32_t* list, uint64_t n_work) -> int {  // HBM bitonic sort regions
+    uint64_t slots = 0;
+    CCRDT_TRY(hbm_regions(e, list, n_work, nullptr, a.cnt, 1, 1, &slots));
+    CCRDT_TRY(T.hb_a.ensure(slots * 8));
+    CCRDT_TRY(T.hb_b.ensure(slots * 8));
+    a.g_id = T.hb_a.as<int64_t>();
+    a.g_score = T.hb_b.as<int64_t>();
+    return CCRDT_OK;
+  };
+  // (untimed: last_kernel_ms stays the last apply's)
+  CCRDT_TRY(class_ladder(e, a, 3, nullptr, nullptr, hbm, topk_launch_value));
   CCRDT_HIP(hipMemcpy(ptr, T.stage[4].p, (nk + 1) * 8, hipMemcpyDeviceToHost));
   if (total) {
     CCRDT_HIP(hipMemcpy(id, T.stage[2].p, total * 8, hipMemcpyDeviceToHost));
@@ -658,51 +694,26 @@ int ccrdt_lb_apply_device(ccrdt_engine* e, const ccrdt_lb_ops* ops) {
   a.ex_cnt = T.ex_cnt.as<uint32_t>();
   a.ex = T.ex.as<LbExtraRec>();
   a.status = T.status.as<uint32_t>();
-  {
-    const char* sq = getenv("CCRDT_LB_SEQ");
-    a.seq = (sq && sq[0] == '1') ? 1 : 0;
-  }
-  uint64_t n_work = nk;
-  const uint32_t* list = nullptr;
+  a.seq = WcHooks::lb_seq() ? 1 : 0;
   float total_ms = 0.f;
   // LDS classes: 512 / 640 / 1024 entries for boards whose Ids and Scores fit
   // 32 bits, then 512 / 640 / 1024 / 2048 entries of 64-bit values, then HBM
   // boards (lb_launch_apply)
-  for (int cls = 0; cls < 8 && n_work; ++cls) {
-    DevBuf* ovf = (list == T.ovf_a.as<uint32_t>()) ? &T.ovf_b : &T.ovf_a;
-    a.key_list = list;
-    a.ovf_list = ovf->as<uint32_t>();
-    if (cls == 7) {  // HBM boards: entries + a 2x hash per board
-      uint64_t slots = 0;
-      CCRDT_TRY(hbm_regions(e, list, n_work, ops->key_ptr,
-                            e->fresh ? nullptr : (const uint32_t*)a.meta_in + 1, 4, 1, &slots));
-      CCRDT_TRY(T.hb_a.ensure(slots * 8));
-      CCRDT_TRY(T.hb_b.ensure(slots * 8));
-      CCRDT_TRY(T.hb_c.ensure(slots));
-      CCRDT_TRY(T.hb_d.ensure(slots * 8));
-      a.tab_off = T.hb_off.as<uint64_t>();
-      a.tab_cap = T.hb_cap.as<uint32_t>();
-      a.g_eid = T.hb_a.as<int64_t>();
-      a.g_esc = T.hb_b.as<int64_t>();
-      a.g_est = T.hb_c.as<uint8_t>();
-      a.g_hslot = T.hb_d.as<uint32_t>();
-    }
-    CCRDT_HIP(hipMemsetAsync(T.status.p, 0, 8, e->stream));
-    CCRDT_HIP(hipEventRecord(e->evk0, e->stream));
-    CCRDT_TRY(lb_launch_apply(a, cls, n_work, e->stream));
-    CCRDT_HIP(hipEventRecord(e->evk1, e->stream));
-    uint32_t st[2];
-    CCRDT_TRY(read_status(e, st));
-    float ms = 0.f;
-    CCRDT_HIP(hipEventElapsedTime(&ms, e->evk0, e->evk1));
-    total_ms += ms;
-    if (st[1]) {
-      set_error("lb_apply: effect kind > 2 (no function clause)");
-      return CCRDT_EINVAL;
-    }
-    n_work = st[0];
-    list = ovf->as<uint32_t>();
-  }
+  auto hbm = [&](const uint32_t* list, uint64_t n_work) -> int {  // HBM boards: entries + a 2x hash per board
+    uint64_t slots = 0;
+    CCRDT_TRY(hbm_regions(e, list, n_work, ops->key_ptr,
+                          e->fresh ? nullptr : (const uint32_t*)a.meta_in + 1, 4, 1, &slots));
+    CCRDT_TRY(T.hb_a.ensure(slots * 8));
+    CCRDT_TRY(T.hb_b.ensure(slots * 8));
+    CCRDT_TRY(T.hb_c.ensure(slots));
+    CCRDT_TRY(T.hb_d.ensure(slots * 8));
+    a.g_eid = T.hb_a.as<int64_t>();
+    a.g_esc = T.hb_b.as<int64_t>();
+    a.g_est = T.hb_c.as<uint8_t>();
+    a.g_hslot = T.hb_d.as<uint32_t>();
+    return CCRDT_OK;
+  };
+  CCRDT_TRY(class_ladder(e, a, 8, &total_ms, "lb_apply: effect kind > 2 (no function clause)", hbm, lb_launch_apply));
   CCRDT_HIP(hipMemcpyAsync(T.kp.p, ops->key_ptr, (nk + 1) * 8, hipMemcpyDeviceToDevice, e->stream));
   e->last_kernel_ms = total_ms;
   e->last_n_ops = n_ops;
@@ -803,21 +814,7 @@ int lb_download(ccrdt_engine* e, LbHost& h, uint64_t k0, uint64_t k1) {
 }  // namespace
 
 int ccrdt_lb_state_sizes(ccrdt_engine* e, int64_t* n_obs, int64_t* n_masked, int64_t* n_bans) {
-  CCRDT_TRY(check_type(e, CCRDT_LEADERBOARD));
-  LbHost h;
-  CCRDT_TRY(lb_download(e, h, 0, (uint64_t)e->n_keys));
-  int64_t o = 0, m = 0, b = 0;
-  for (const LbMeta& mt : h.meta)
-    for (uint32_t j = 0; j < mt.n; ++j) {
-      const uint8_t s = h.st[mt.off + j];
-      o += s == LB_OBS;
-      m += s == LB_MASKED;
-      b += s == LB_BANNED;
-    }
-  *n_obs = o;
-  *n_masked = m;
-  *n_bans = b;
-  return CCRDT_OK;
+  return ccrdt_lb_range_sizes(e, 0, e ? e->n_keys : 0, n_obs, n_masked, n_bans);
 }
 
 int ccrdt_lb_export(ccrdt_engine* e, ccrdt_lb_state* out) {
@@ -1023,7 +1020,7 @@ static uint64_t pow2_at_least(uint64_t x) {
   return p;
 }
 
-static uint64_t wc_next_seed(uint64_t z) {  // splitmix64 step
+static uint64_t wc_next_seed(uint64_t z) {  // splitmix64 step (cluster.splitmix64: also the words' owner hash)
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -1040,24 +1037,374 @@ static WcArgs wc_table_args(ccrdt_engine* e, int side) {
   a.t_cnt = T.t_cnt[side].as<unsigned long long>();
   a.t_mask = T.t_slots[side] ? T.t_slots[side] - 1 : 0;
   a.seed = T.wc_seed;
-  a.weak0 = getenv("CCRDT_WC_WEAK0") ? 1 : 0;
+  a.weak0 = WcHooks::weak0() ? 1 : 0;
   a.arena = T.arena.as<uint8_t>();
   a.status = T.status.as<uint32_t>();
   return a;
 }
 
-static int wc_alloc_table(ccrdt_engine* e, int side, uint64_t slots) {
+// The other side of the word table, emptied at `slots` slots, with (carry) the
+// current side's words rehashed into it; a = the kernel arguments of that side.
+static int wc_new_table(ccrdt_engine* e, uint64_t slots, bool carry, WcArgs& a) {
   TypeBufs& T = e->tb;
+  const int in = T.tcur, out = 1 - T.tcur;
   if (slots > (1ull << 32)) {  // (check records hold 32-bit slot indices)
     set_error("wc: word table above 2^32 slots");
     return CCRDT_ENOMEM;
   }
-  CCRDT_TRY(T.t_tab[side].ensure(slots * sizeof(WcSlot)));
-  CCRDT_TRY(T.t_meta[side].ensure(slots * sizeof(WcMeta)));
-  CCRDT_TRY(T.t_cnt[side].ensure(slots * 8));
-  CCRDT_HIP(hipMemsetAsync(T.t_tab[side].p, 0, slots * sizeof(WcSlot), e->stream));
-  CCRDT_HIP(hipMemsetAsync(T.t_cnt[side].p, 0, slots * 8, e->stream));
-  T.t_slots[side] = slots;
+  CCRDT_TRY(T.t_tab[out].ensure(slots * sizeof(WcSlot)));
+  CCRDT_TRY(T.t_meta[out].ensure(slots * sizeof(WcMeta)));
+  CCRDT_TRY(T.t_cnt[out].ensure(slots * 8));
+  CCRDT_HIP(hipMemsetAsync(T.t_tab[out].p, 0, slots * sizeof(WcSlot), e->stream));
+  CCRDT_HIP(hipMemsetAsync(T.t_cnt[out].p, 0, slots * 8, e->stream));
+  T.t_slots[out] = slots;
+  a = wc_table_args(e, out);
+  if (carry && T.t_slots[in])
+    CCRDT_TRY(wc_launch_rehash(T.t_tab[in].as<WcSlot>(), T.t_meta[in].as<WcMeta>(),
+                               T.t_cnt[in].as<unsigned long long>(), T.t_slots[in], a, e->stream));
+  return CCRDT_OK;
+}
+
+// Arena room for `need` more bytes after the `used` ones, + `slack` bytes a
+// kernel may read past a word; a grown arena holds twice the bytes.
+static int wc_grow_arena(ccrdt_engine* e, uint64_t used, uint64_t need, uint64_t slack) {
+  TypeBufs& T = e->tb;
+  if (used + need + slack <= T.arena_cap) return CCRDT_OK;
+  DevBuf grown;
+  const uint64_t cap = std::max<uint64_t>(2 * (used + need) + slack, 4096);
+  CCRDT_TRY(grown.ensure(cap));
+  if (used) CCRDT_HIP(hipMemcpyAsync(grown.p, T.arena.p, used, hipMemcpyDeviceToDevice, e->stream));
+  CCRDT_HIP(hipStreamSynchronize(e->stream));
+  T.arena.release();
+  T.arena = grown;
+  grown.p = nullptr;
+  T.arena_cap = cap;
+  return CCRDT_OK;
+}
+
+namespace {
+// (CCRDT_WC_ROUTE_GROW_BITS reports status word WC_ST_GROW as it is)
+static_assert(WC_GROW_TABLE == CCRDT_WC_GROW_TABLE && WC_GROW_DEDUPE == CCRDT_WC_GROW_DEDUPE);
+static_assert(WC_GROW_COUNT_LIST == CCRDT_WC_GROW_COUNT_LIST && WC_GROW_DOC_LIST == CCRDT_WC_GROW_DOC_LIST);
+
+// ccrdt_wc_apply_device in steps: the batch plan (wc_plan_layout,
+// wc_plan_sizes), built once; then attempts -- wc_begin_attempt,
+// wc_insert_launches, and either wc_regrow and again, or wc_count_list_sum,
+// wc_persist_and_check and the commit (wc_rollback and a new seed on a hash
+// collision).
+struct WcLaunch { uint64_t d0, d1, tokens; };  // documents [d0, d1) of the batch and their tokens
+struct WcPlan {
+  const ccrdt_wc_docs* docs;
+  const bool wdc;
+  const uint64_t nd;
+  // layout (wc_plan_layout): tokens per document (worddocumentcount; else
+  // zeros) and of the batch (wordcount: an upper bound), first chunk and first
+  // group of each document, chunk -> document and group -> document (these
+  // two live until the batch is done)
+  std::vector<uint64_t> ntok, tptr, gptr;
+  std::vector<uint32_t> cdoc, gdoc;
+  uint64_t tokens = 0, words_old = 0, arena_used = 0;  // (the last two: the state before the batch)
+  // sizes and hooks (wc_plan_sizes)
+  uint64_t slots0, chk_cap, n_chunks, n_fl, n_tb, dtags;
+  uint32_t shard_blocks, fl_tab;
+  bool count_list, doc_lists;
+  std::vector<uint64_t> dl_rn;  // document-list region of each document
+  std::vector<WcLaunch> launches;
+  uint64_t max_rn = 0, max_docs = 0;  // the largest launch's regions and documents
+};
+
+static int wc_plan_layout(ccrdt_engine* e, WcPlan& P) {
+  TypeBufs& T = e->tb;
+  const ccrdt_wc_docs* docs = P.docs;
+  const uint64_t nd = P.nd, nk = (uint64_t)e->n_keys;
+  // document keys and token counts
+  CCRDT_TRY(T.stage[0].ensure(nd * 8 + 8));
+  CCRDT_TRY(T.stage[1].ensure(nd * 8 + 8));
+  CCRDT_TRY(wc_launch_doc_key(docs->key_ptr, nk, nd, T.stage[0].as<uint64_t>(), e->stream));
+  // tokens per document: worddocumentcount sizes its (document, word) dedupe
+  // table by them; wordcount only sizes its word table, for which the bound
+  // bytes + documents will do (the table regrows if a batch overflows it)
+  if (P.wdc) {
+    CCRDT_TRY(wc_launch_count(docs->doc_off, docs->bytes, nd, T.stage[1].as<uint64_t>(), e->stream));
+    CCRDT_TRY(d2h(P.ntok, T.stage[1], nd, e->stream));
+    for (uint64_t t : P.ntok) P.tokens += t;
+  } else {
+    P.ntok.assign(nd, 0);
+    P.tokens = docs->n_bytes + nd;
+  }
+  // documents -> chunks of WC_TPW tiles of WC_TILE bytes (one wave each)
+  std::vector<uint64_t> doff(nd + 1);
+  std::vector<uint64_t>&tptr = P.tptr, &gptr = P.gptr;
+  tptr.assign(nd + 1, 0);
+  if (nd) {
+    CCRDT_HIP(hipMemcpyAsync(doff.data(), docs->doc_off, (nd + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+    CCRDT_HIP(hipStreamSynchronize(e->stream));
+  }
+  for (uint64_t d = 0; d < nd; ++d)
+    tptr[d + 1] = tptr[d] + ((doff[d + 1] - doff[d]) / WC_TILE + WC_TPW) / WC_TPW;
+  CCRDT_TRY(h2d(*e, T.stage[4], tptr.data(), (nd + 1) * 8));
+  if (nd > 0xFFFFFFFFull) {
+    set_error("wc_apply: more than 2^32 documents in one batch");
+    return CCRDT_EINVAL;
+  }
+  std::vector<uint32_t> cdoc(tptr[nd] + 1, 0u);
+  P.cdoc.swap(cdoc);
+  for (uint64_t d = 0; d < nd; ++d)
+    for (uint64_t c = tptr[d]; c < tptr[d + 1]; ++c) P.cdoc[c] = (uint32_t)d;
+  CCRDT_TRY(h2d(*e, T.stage[5], P.cdoc.data(), P.cdoc.size() * 4));
+  // worddocumentcount: groups of WC_WAVES_WDC chunks of one document (one workgroup each)
+  gptr.assign(nd + 1, 0);
+  if (P.wdc) {
+    for (uint64_t d = 0; d < nd; ++d) gptr[d + 1] = gptr[d] + (tptr[d + 1] - tptr[d] + WC_WAVES_WDC - 1) / WC_WAVES_WDC;
+    P.gdoc.resize(gptr[nd] + 1, 0u);
+    for (uint64_t d = 0; d < nd; ++d)
+      for (uint64_t g = gptr[d]; g < gptr[d + 1]; ++g) P.gdoc[g] = (uint32_t)d;
+    CCRDT_TRY(h2d(*e, T.stage[6], gptr.data(), (nd + 1) * 8));
+    CCRDT_TRY(h2d(*e, T.stage[7], P.gdoc.data(), P.gdoc.size() * 4));
+  }
+  return CCRDT_OK;
+}
+
+static int wc_plan_sizes(ccrdt_engine* e, WcPlan& P) {
+  TypeBufs& T = e->tb;
+  const uint64_t nd = P.nd, n_bytes = P.docs->n_bytes;
+  // (a batch's new words are guessed at <= 2^20: the table then stays
+  // resident in the 256 MiB Infinity Cache; a batch with more overflows it and
+  // is re-run on a table four times larger)
+  P.slots0 = WcHooks::slots(pow2_at_least(2 * (P.words_old + std::min<uint64_t>(P.tokens, 1ull << 20))));
+  // the check list: tokens whose identity the insert kernel leaves open
+  // (words of more than WC_SHORT bytes; slots whose identity was not yet
+  // visible); a batch that fills it is verified token by token instead
+  P.chk_cap = WcHooks::chk_cap(std::min<uint64_t>(n_bytes / 128 + 65536, 1ull << 27));
+  CCRDT_TRY(T.chk.ensure(std::max<uint64_t>(P.chk_cap, 1) * sizeof(WcChk)));
+  // the count list (WcArgs::cl): token blocks for the LDS misses' counts
+  // (room for a sixteenth of the bytes plus a block per chunk), one flush
+  // region per insert workgroup; without it the device adds
+  P.n_chunks = P.tptr[nd];
+  P.count_list = !WcHooks::no_list();
+  const uint64_t cl_blocks = (n_bytes / 16 + P.n_chunks * WC_BLK) / WC_BLK;
+  P.shard_blocks = (uint32_t)WcHooks::cl_blocks(
+      std::min<uint64_t>((cl_blocks + WC_NSHARD - 1) / WC_NSHARD + 1, 0xFFFFFFFFull / WC_BLK / WC_NSHARD));
+  P.n_tb = (uint64_t)WC_NSHARD * P.shard_blocks;
+  P.fl_tab = P.wdc ? WC_TAB_WDC : WC_TAB_WC;
+  P.n_fl = P.wdc ? P.gptr[nd] : (P.n_chunks + WC_WAVES_WC - 1) / WC_WAVES_WC;
+  // worddocumentcount: document lists instead of the dedupe table (the dedupe
+  // table also when the word table needs more than WC_DL_MAXPASS bitmap
+  // passes, or a document's list overflows); region of a document: twice its
+  // tokens + a block per wave (wc_dl_push)
+  P.doc_lists = P.wdc && WcHooks::doc_lists();
+  P.dl_rn.assign(P.doc_lists ? nd : 0, 0);
+  if (P.doc_lists && nd) {
+    std::vector<uint64_t> pre(nd + 1, 0);
+    for (uint64_t d = 0; d < nd; ++d) {
+      P.dl_rn[d] = 2 * P.ntok[d] + (P.gptr[d + 1] - P.gptr[d]) * WC_WAVES_WDC * WC_DL_BLK;
+      pre[d + 1] = pre[d] + P.dl_rn[d];
+    }
+    CCRDT_TRY(h2d(*e, T.dl_pre, pre.data(), (nd + 1) * 8));
+  }
+  // the insert launches.  wordcount: one.  worddocumentcount: its dedupe table
+  // is sized by a launch's tokens, so runs of documents of <= 2^28 tokens, and
+  // (dedupe entries hold a document tag in 24 bits) < 2^23 documents.  The
+  // document lists are sized once, for the largest launch.
+  const uint64_t launch_tok = WcHooks::launch_tokens(1ull << 28);
+  for (uint64_t d0 = 0; d0 < nd;) {
+    WcLaunch L{d0, d0, 0};
+    while (L.d1 < nd && (L.d1 == d0 || !P.wdc || (L.tokens + P.ntok[L.d1] <= launch_tok && L.d1 - d0 < (1ull << 23))))
+      L.tokens += P.ntok[L.d1++];
+    uint64_t rn = 0;
+    for (uint64_t x = d0; x < L.d1 && P.doc_lists; ++x) rn += P.dl_rn[x];
+    P.max_rn = std::max(P.max_rn, rn);
+    P.max_docs = std::max(P.max_docs, L.d1 - d0);
+    P.launches.push_back(L);
+    d0 = L.d1;
+  }
+  P.dtags = WcHooks::dtags(1ull << 24);
+  return CCRDT_OK;
+}
+
+// What changes from one attempt at a batch to the next.  T.wc_seed and the
+// dedupe table's T.d_base / T.d_clean live on the engine: they persist across
+// attempts and batches.
+struct WcAttempt {
+  uint64_t slots;       // of the word table
+  bool use_cl, use_dl;  // the count list / the document lists are still allowed
+  uint64_t dmul = 1;    // worddocumentcount dedupe table: multiple of its first size
+  bool reseeded = false;
+  // this attempt's routes, from slots (wc_begin_attempt)
+  uint32_t bsh = 0, dl_passes = 0;
+  bool cl_on = false, dl_on = false;
+};
+}  // namespace
+
+// Status word WC_ST_GROW of an attempt -> the next attempt.  (A full dedupe
+// table or document list cannot be reached from inputs at the present sizing --
+// two slots per token, regions of twice the tokens -- and no hook forces them;
+// their handling is kept for a sizing that changes.)
+static void wc_regrow(WcAttempt& at, uint32_t grow) {
+  if (grow & WC_GROW_TABLE) at.slots *= 4;
+  if (grow & WC_GROW_DEDUPE) at.dmul *= 4;
+  if (grow & WC_GROW_COUNT_LIST) at.use_cl = false;
+  if (grow & WC_GROW_DOC_LIST) at.use_dl = false;
+}
+
+// New table (rehash of the current words), cleared status, and the attempt's
+// routes with their buffers: a = the insert kernel's arguments but for the
+// per-launch ones.
+static int wc_begin_attempt(ccrdt_engine* e, const WcPlan& P, WcAttempt& at, WcArgs& a) {
+  TypeBufs& T = e->tb;
+  CCRDT_TRY(wc_new_table(e, at.slots, !e->fresh, a));
+  CCRDT_HIP(hipMemsetAsync(T.status.p, 0, 16, e->stream));
+  a.chk = T.chk.as<WcChk>();
+  a.chk_cap = (uint32_t)std::min<uint64_t>(P.chk_cap, 0xFFFFFFFFull);
+  // (bucket sums: buckets of 2^WC_CL_MAXSH slots -- few buckets, so the
+  // scatter pass writes long runs -- at most WC_CL_NB of them)
+  uint32_t lg = 0;
+  while ((1ull << lg) < at.slots) ++lg;
+  at.bsh = std::min<uint32_t>(lg, WC_CL_MAXSH);
+  at.cl_on = at.use_cl && (at.slots >> at.bsh) <= WC_CL_NB && P.n_tb * WC_BLK + P.n_fl * P.fl_tab < (1ull << 32);
+  at.dl_passes = (uint32_t)((at.slots + WC_DL_BITS - 1) / WC_DL_BITS);
+  at.dl_on = at.use_dl && at.dl_passes <= WC_DL_MAXPASS;
+  if (at.cl_on) {
+    CCRDT_TRY(T.cl.ensure(P.n_tb * WC_BLK * 4));
+    CCRDT_TRY(T.cl_bcnt.ensure(P.n_tb * 4));
+    CCRDT_TRY(T.fl.ensure(std::max<uint64_t>(P.n_fl * P.fl_tab, 1) * 8));
+    CCRDT_TRY(T.cl_small.ensure((WC_NSHARD + 2 * WC_CL_NB) * 4 + (WC_CL_NB + 1) * 8));
+    CCRDT_HIP(hipMemsetAsync(T.cl_small.p, 0, (WC_NSHARD + 2 * WC_CL_NB) * 4, e->stream));
+    a.cl = T.cl.as<uint32_t>();
+    a.cl_bcnt = T.cl_bcnt.as<uint32_t>();
+    a.cl_cur = T.cl_small.as<uint32_t>();
+    a.cl_shard_blocks = P.shard_blocks;
+    a.fl = at.dl_on ? nullptr : T.fl.as<uint64_t>();  // (document lists: the flush appends pairs instead)
+  }
+  a.bytes = P.docs->bytes;
+  a.n_bytes = P.docs->n_bytes;
+  return CCRDT_OK;
+}
+
+// worddocumentcount's (document, word) dedupe table for one launch: two slots
+// per token (measured: half a slot per token overflowed on the Zipf corpus and
+// the re-run cost 13 ms); an overflow re-runs the batch with four times the
+// slots.  Not cleared per launch: the launch's document tags lie above every
+// earlier launch's (WcArgs::d_base), so the old pairs read as free; only a new
+// buffer, slots never cleared, or spent tags (P.dtags, 2^24) clear.
+static int wc_dedupe_table(ccrdt_engine* e, const WcPlan& P, const WcLaunch& L, uint64_t dmul, WcArgs& a) {
+  TypeBufs& T = e->tb;
+  const uint64_t ds = pow2_at_least(std::max<uint64_t>(2 * L.tokens, 1024) * dmul);
+  const uint64_t b0 = T.d_hash.bytes;
+  CCRDT_TRY(T.d_hash.ensure(ds * 8));
+  if (T.d_hash.bytes != b0) T.d_clean = T.d_base = 0;
+  if (T.d_base + (L.d1 - L.d0) >= P.dtags || WcHooks::dclear()) {  // (the hook, a diagnostic: every launch)
+    T.d_clean = std::max(T.d_clean, ds);
+    CCRDT_HIP(hipMemsetAsync(T.d_hash.p, 0, T.d_clean * 8, e->stream));
+    T.d_base = 0;
+  } else if (ds > T.d_clean) {
+    CCRDT_HIP(hipMemsetAsync(T.d_hash.as<uint64_t>() + T.d_clean, 0, (ds - T.d_clean) * 8, e->stream));
+    T.d_clean = ds;
+  }
+  a.dl = nullptr;
+  a.d_hash = T.d_hash.as<uint64_t>();
+  a.d_mask = ds - 1;
+  a.d_base = T.d_base;
+  T.d_base += L.d1 - L.d0;
+  return CCRDT_OK;
+}
+
+// a's view of the documents [d0, d1) of the batch (one launch's, or all).
+static void wc_doc_window(TypeBufs& T, const WcPlan& P, uint64_t d0, uint64_t d1, WcArgs& a) {
+  a.n_docs = (int64_t)(d1 - d0);
+  a.doc_key = T.stage[0].as<uint64_t>() + d0;
+  a.doc_off = P.docs->doc_off + d0;
+  a.tile_ptr = T.stage[4].as<uint64_t>() + d0;
+  a.tile0 = P.tptr[d0];
+  a.chunk_doc = T.stage[5].as<uint32_t>();
+  a.doc0 = d0;
+}
+
+// The insert kernel over the plan's launches (and, with document lists, the
+// list kernel after each).
+static int wc_insert_launches(ccrdt_engine* e, const WcPlan& P, const WcAttempt& at, WcArgs& a) {
+  TypeBufs& T = e->tb;
+  for (const WcLaunch& L : P.launches) {
+    const uint64_t d0 = L.d0, d1 = L.d1;
+    wc_doc_window(T, P, d0, d1, a);
+    if (a.wdc) {
+      a.group_doc = T.stage[7].as<uint32_t>();
+      a.group_ptr = T.stage[6].as<uint64_t>() + d0;
+      a.group0 = P.gptr[d0];
+      a.n_groups = P.gptr[d1] - P.gptr[d0];
+    }
+    if (a.wdc && at.dl_on) {
+      CCRDT_TRY(T.dl.ensure(std::max<uint64_t>(P.max_rn, 1) * 4));
+      CCRDT_TRY(T.dl_cur.ensure(std::max<uint64_t>(P.max_docs, 1) * 4));
+      CCRDT_HIP(hipMemsetAsync(T.dl_cur.p, 0, (d1 - d0) * 4, e->stream));
+      a.dl = T.dl.as<uint32_t>();
+      a.dl_pre = T.dl_pre.as<uint64_t>() + d0;
+      a.dl_cur = T.dl_cur.as<uint32_t>();
+      a.d_hash = nullptr;
+    } else if (a.wdc) {
+      CCRDT_TRY(wc_dedupe_table(e, P, L, at.dmul, a));
+    }
+    a.fl_base = a.wdc ? a.group0 : 0;  // (wordcount: one launch)
+    a.dbg = WcHooks::idbg();
+    CCRDT_TRY(wc_launch_insert(a, P.tptr[d1] - P.tptr[d0], e->stream));
+    a.dbg = 0;
+    if (a.wdc && at.dl_on) CCRDT_TRY(wc_launch_dl(a, d1 - d0, at.dl_passes, e->stream));
+  }
+  return CCRDT_OK;
+}
+
+// The count list summed into the counts, per bucket of slots.
+static int wc_count_list_sum(ccrdt_engine* e, const WcPlan& P, const WcAttempt& at, const WcArgs& a) {
+  TypeBufs& T = e->tb;
+  WcClArgs c{};
+  c.cl = T.cl.as<uint32_t>();
+  c.bcnt = T.cl_bcnt.as<uint32_t>();
+  c.cur = T.cl_small.as<uint32_t>();
+  c.shard_blocks = P.shard_blocks;
+  c.fl = T.fl.as<uint64_t>();
+  c.tab = P.fl_tab;
+  c.n_tb = P.n_tb;
+  c.n_fl = at.dl_on ? 0 : P.n_fl;
+  c.bsh = at.bsh;
+  c.nb = (uint32_t)(at.slots >> at.bsh);
+  c.bkt_cnt = T.cl_small.as<uint32_t>() + WC_NSHARD;
+  c.bkt_cur = c.bkt_cnt + WC_CL_NB;
+  c.bkt_off = reinterpret_cast<uint64_t*>(c.bkt_cur + WC_CL_NB);
+  c.t_cnt = a.t_cnt;
+  c.status = a.status;
+  CCRDT_TRY(wc_launch_cl_count(c, e->stream));
+  std::vector<uint64_t> tot;
+  CCRDT_TRY(d2h_at(tot, T.cl_small, (WC_NSHARD + 2 * WC_CL_NB) / 2 + c.nb, 1, e->stream));
+  CCRDT_TRY(T.bkt.ensure(std::max<uint64_t>(tot[0], 1) * 4));
+  c.bkt = T.bkt.as<uint32_t>();
+  return wc_launch_cl_sum(c, e->stream);
+}
+
+// The batch's new words into the arena first (the check list's long words are
+// compared against a compact, cache-resident copy), then exactness: every
+// token equals its word's identity -- the insert kernel compared all but the
+// check list's tokens (a full list, or CCRDT_WC_VERIFY: every token again).
+// st (WC_ST_* words): the insert's read-back in, the check's out.
+static int wc_persist_and_check(ccrdt_engine* e, const WcPlan& P, WcArgs& a, uint32_t* st) {
+  TypeBufs& T = e->tb;
+  wc_doc_window(T, P, 0, P.nd, a);
+  a.group_doc = nullptr;
+  a.arena = T.arena.as<uint8_t>();
+  CCRDT_HIP(hipMemsetAsync((uint64_t*)T.arena_top.p + 1, 0, 8, e->stream));
+  CCRDT_TRY(wc_launch_persist(a, T.arena.as<uint8_t>(), T.arena_top.as<unsigned long long>(), e->stream));
+  const bool full = (st[WC_ST_ERR] & WC_CHK_FULL) || WcHooks::verify();
+  T.wc_checks = full ? -1 : (int64_t)st[WC_ST_CHECKS];
+  if (full) CCRDT_TRY(wc_launch_verify(a, P.n_chunks, e->stream));
+  else CCRDT_TRY(wc_launch_check(a, st[WC_ST_CHECKS], e->stream));
+  return read_status(e, st);
+}
+
+// The state as it was before the batch: the new table side is dropped (tcur
+// has not moved), the arena top goes back to the words it held.
+static int wc_rollback(ccrdt_engine* e, const WcPlan& P) {
+  const uint64_t back[2] = {P.arena_used, P.words_old};
+  CCRDT_TRY(h2d(*e, e->tb.arena_top, back, 16));
+  CCRDT_HIP(hipStreamSynchronize(e->stream));
   return CCRDT_OK;
 }
 
@@ -1069,320 +1416,84 @@ int ccrdt_wc_apply_device(ccrdt_engine* e, const ccrdt_wc_docs* docs) {
   }
   if (e->n_keys > 0xFFFFFFFFll) return CCRDT_EINVAL;
   TypeBufs& T = e->tb;
-  const uint64_t nd = (uint64_t)docs->n_docs, nk = (uint64_t)e->n_keys;
+  int64_t* route = T.wc_route;
+  std::fill(route, route + CCRDT_WC_N_ROUTE, 0);
   CCRDT_TRY(T.status.ensure(64));
   CCRDT_TRY(T.arena_top.ensure(16));
   if (e->fresh) {
     CCRDT_HIP(hipMemsetAsync(T.arena_top.p, 0, 16, e->stream));
     T.t_slots[T.tcur] = 0;
   }
-  // document keys and token counts
-  CCRDT_TRY(T.stage[0].ensure(nd * 8 + 8));
-  CCRDT_TRY(T.stage[1].ensure(nd * 8 + 8));
-  CCRDT_TRY(wc_launch_doc_key(docs->key_ptr, nk, nd, T.stage[0].as<uint64_t>(), e->stream));
-  // tokens per document: worddocumentcount sizes its (document, word) dedupe
-  // table by them; wordcount only sizes its word table, for which the bound
-  // bytes + documents will do (the table regrows if a batch overflows it)
-  std::vector<uint64_t> ntok;
-  uint64_t tokens = 0;
-  if (e->type == CCRDT_WORDDOCUMENTCOUNT) {
-    CCRDT_TRY(wc_launch_count(docs->doc_off, docs->bytes, nd, T.stage[1].as<uint64_t>(), e->stream));
-    CCRDT_TRY(d2h(ntok, T.stage[1], nd, e->stream));
-    for (uint64_t t : ntok) tokens += t;
-  } else {
-    ntok.assign(nd, 0);
-    tokens = docs->n_bytes + nd;
-  }
-  // documents -> chunks of WC_TPW tiles of WC_TILE bytes (one wave each)
-  std::vector<uint64_t> doff(nd + 1), tptr(nd + 1);
-  if (nd) {
-    CCRDT_HIP(hipMemcpyAsync(doff.data(), docs->doc_off, (nd + 1) * 8, hipMemcpyDeviceToHost, e->stream));
-    CCRDT_HIP(hipStreamSynchronize(e->stream));
-  }
-  tptr[0] = 0;
-  for (uint64_t d = 0; d < nd; ++d)
-    tptr[d + 1] = tptr[d] + ((doff[d + 1] - doff[d]) / WC_TILE + WC_TPW) / WC_TPW;
-  CCRDT_TRY(h2d(*e, T.stage[4], tptr.data(), (nd + 1) * 8));
-  if (nd > 0xFFFFFFFFull) {
-    set_error("wc_apply: more than 2^32 documents in one batch");
-    return CCRDT_EINVAL;
-  }
-  std::vector<uint32_t> cdoc(tptr[nd] + 1, 0u);  // chunk -> document (lives until the batch is done)
-  for (uint64_t d = 0; d < nd; ++d)
-    for (uint64_t c = tptr[d]; c < tptr[d + 1]; ++c) cdoc[c] = (uint32_t)d;
-  CCRDT_TRY(h2d(*e, T.stage[5], cdoc.data(), cdoc.size() * 4));
-  // worddocumentcount: groups of WC_WAVES_WDC chunks of one document (one workgroup each)
-  std::vector<uint64_t> gptr(nd + 1, 0);
-  std::vector<uint32_t> gdoc;
-  if (e->type == CCRDT_WORDDOCUMENTCOUNT) {
-    for (uint64_t d = 0; d < nd; ++d) gptr[d + 1] = gptr[d] + (tptr[d + 1] - tptr[d] + WC_WAVES_WDC - 1) / WC_WAVES_WDC;
-    gdoc.resize(gptr[nd] + 1, 0u);
-    for (uint64_t d = 0; d < nd; ++d)
-      for (uint64_t g = gptr[d]; g < gptr[d + 1]; ++g) gdoc[g] = (uint32_t)d;
-    CCRDT_TRY(h2d(*e, T.stage[6], gptr.data(), (nd + 1) * 8));
-    CCRDT_TRY(h2d(*e, T.stage[7], gdoc.data(), gdoc.size() * 4));
-  }
+  WcPlan P{docs, e->type == CCRDT_WORDDOCUMENTCOUNT, (uint64_t)docs->n_docs};
+  CCRDT_TRY(wc_plan_layout(e, P));
   std::vector<uint64_t> top;
   CCRDT_TRY(d2h(top, T.arena_top, 2, e->stream));
-  const uint64_t words_old = e->fresh ? 0 : top[1], arena_used = e->fresh ? 0 : top[0];
+  P.words_old = e->fresh ? 0 : top[1];
+  P.arena_used = e->fresh ? 0 : top[0];
   // arena: room for every byte of the batch (upper bound of new word bytes)
   // (+32: the verify pass reads three aligned 8-byte words around a word)
-  if (arena_used + docs->n_bytes + 32 > T.arena_cap) {
-    DevBuf grown;
-    const uint64_t cap = std::max<uint64_t>(2 * (arena_used + docs->n_bytes) + 32, 4096);
-    CCRDT_TRY(grown.ensure(cap));
-    if (arena_used)
-      CCRDT_HIP(hipMemcpyAsync(grown.p, T.arena.p, arena_used, hipMemcpyDeviceToDevice, e->stream));
-    CCRDT_HIP(hipStreamSynchronize(e->stream));
-    T.arena.release();
-    T.arena = grown;
-    grown.p = nullptr;
-    T.arena_cap = cap;
-  }
-  const int in = T.tcur, out = 1 - T.tcur;
-  // (a batch's new words are guessed at <= 2^20: the table then stays
-  // resident in the 256 MiB Infinity Cache; a batch with more overflows it and
-  // is re-run on a table four times larger)
-  uint64_t slots = pow2_at_least(2 * (words_old + std::min<uint64_t>(tokens, 1ull << 20)));
-  bool reseeded = false;
-  uint64_t dmul = 1;  // worddocumentcount dedupe table: multiple of its first size
-  if (getenv("CCRDT_WC_SLOTS")) slots = strtoull(getenv("CCRDT_WC_SLOTS"), nullptr, 0);
-  // the check list: tokens whose identity the insert kernel leaves open
-  // (words of more than WC_SHORT bytes; slots whose identity was not yet
-  // visible); a batch that fills it is verified token by token instead
-  // (CCRDT_WC_CHK_CAP: test hook for the list's capacity)
-  uint64_t chk_cap = std::min<uint64_t>(docs->n_bytes / 128 + 65536, 1ull << 27);
-  if (getenv("CCRDT_WC_CHK_CAP")) chk_cap = strtoull(getenv("CCRDT_WC_CHK_CAP"), nullptr, 0);
-  CCRDT_TRY(T.chk.ensure(std::max<uint64_t>(chk_cap, 1) * sizeof(WcChk)));
-  // the count list (WcArgs::cl): token blocks for the LDS misses' counts
-  // (room for a sixteenth of the bytes plus a block per chunk), one flush
-  // region per insert workgroup; CCRDT_WC_NOLIST=1 keeps the device adds
-  const uint64_t n_chunks = tptr[nd];
-  const bool wdc = e->type == CCRDT_WORDDOCUMENTCOUNT;
-  bool use_cl = !(getenv("CCRDT_WC_NOLIST") && atoi(getenv("CCRDT_WC_NOLIST")));
-  // worddocumentcount: document lists instead of the dedupe table
-  // (CCRDT_WC_DLIST=0: the dedupe table; also when the word table needs more
-  // than WC_DL_MAXPASS bitmap passes, or a document's list overflows)
-  bool use_dl = wdc && !(getenv("CCRDT_WC_DLIST") && !atoi(getenv("CCRDT_WC_DLIST")));
-  // region of a document: twice its tokens + a block per wave (wc_dl_push)
-  std::vector<uint64_t> dl_rn(use_dl ? nd : 0);
-  if (use_dl && nd) {
-    std::vector<uint64_t> pre(nd + 1, 0);
-    for (uint64_t d = 0; d < nd; ++d) {
-      dl_rn[d] = 2 * ntok[d] + (gptr[d + 1] - gptr[d]) * WC_WAVES_WDC * WC_DL_BLK;
-      pre[d + 1] = pre[d] + dl_rn[d];
-    }
-    CCRDT_TRY(h2d(*e, T.dl_pre, pre.data(), (nd + 1) * 8));
-  }
-  const uint64_t cl_entries = docs->n_bytes / 16 + n_chunks * WC_BLK;
-  uint32_t shard_blocks = (uint32_t)std::min<uint64_t>((cl_entries / WC_BLK + WC_NSHARD - 1) / WC_NSHARD + 1,
-                                                       0xFFFFFFFFull / WC_BLK / WC_NSHARD);
-  if (getenv("CCRDT_WC_CL_BLOCKS")) shard_blocks = (uint32_t)strtoul(getenv("CCRDT_WC_CL_BLOCKS"), nullptr, 0);  // test hook
-  const uint64_t n_tb = (uint64_t)WC_NSHARD * shard_blocks;
-  const uint32_t fl_tab = wdc ? WC_TAB_WDC : WC_TAB_WC;
-  const uint64_t n_fl = wdc ? gptr[nd] : (n_chunks + WC_WAVES_WC - 1) / WC_WAVES_WC;
+  CCRDT_TRY(wc_grow_arena(e, P.arena_used, docs->n_bytes, 32));
+  CCRDT_TRY(wc_plan_sizes(e, P));
+  WcAttempt at{P.slots0, P.count_list, P.doc_lists};
   for (int attempt = 0;; ++attempt) {
-    // new table (rehash of the current words), then the batch
-    CCRDT_TRY(wc_alloc_table(e, out, slots));
-    WcArgs a = wc_table_args(e, out);
-    if (!e->fresh && T.t_slots[in])
-      CCRDT_TRY(wc_launch_rehash(T.t_tab[in].as<WcSlot>(), T.t_meta[in].as<WcMeta>(), T.t_cnt[in].as<unsigned long long>(),
-                                 T.t_slots[in], a, e->stream));
-    CCRDT_HIP(hipMemsetAsync(T.status.p, 0, 16, e->stream));
-    a.chk = T.chk.as<WcChk>();
-    a.chk_cap = (uint32_t)std::min<uint64_t>(chk_cap, 0xFFFFFFFFull);
-    // (bucket sums: buckets of 2^WC_CL_MAXSH slots -- few buckets, so the
-    // scatter pass writes long runs -- at most WC_CL_NB of them)
-    uint32_t lg = 0;
-    while ((1ull << lg) < slots) ++lg;
-    const uint32_t bsh = std::min<uint32_t>(lg, WC_CL_MAXSH);
-    const bool cl_on = use_cl && (slots >> bsh) <= WC_CL_NB && n_tb * WC_BLK + n_fl * fl_tab < (1ull << 32);
-    const uint32_t dl_passes = (uint32_t)((slots + WC_DL_BITS - 1) / WC_DL_BITS);
-    const bool dl_on = use_dl && dl_passes <= WC_DL_MAXPASS;
-    if (cl_on) {
-      CCRDT_TRY(T.cl.ensure(n_tb * WC_BLK * 4));
-      CCRDT_TRY(T.cl_bcnt.ensure(n_tb * 4));
-      CCRDT_TRY(T.fl.ensure(std::max<uint64_t>(n_fl * fl_tab, 1) * 8));
-      CCRDT_TRY(T.cl_small.ensure((WC_NSHARD + 2 * WC_CL_NB) * 4 + (WC_CL_NB + 1) * 8));
-      CCRDT_HIP(hipMemsetAsync(T.cl_small.p, 0, (WC_NSHARD + 2 * WC_CL_NB) * 4, e->stream));
-      a.cl = T.cl.as<uint32_t>();
-      a.cl_bcnt = T.cl_bcnt.as<uint32_t>();
-      a.cl_cur = T.cl_small.as<uint32_t>();
-      a.cl_shard_blocks = shard_blocks;
-      a.fl = dl_on ? nullptr : T.fl.as<uint64_t>();  // (document lists: the flush appends pairs instead)
-    }
-    a.doc_off = docs->doc_off;
-    a.bytes = docs->bytes;
-    a.n_bytes = docs->n_bytes;
+    route[CCRDT_WC_ROUTE_ATTEMPTS] = attempt + 1;
+    WcArgs a;
+    CCRDT_TRY(wc_begin_attempt(e, P, at, a));
     CCRDT_HIP(hipEventRecord(e->evk0, e->stream));
-    // worddocumentcount: the (document, word) dedupe table is sized by the
-    // chunk's tokens; documents are processed in chunks of <= 2^28 tokens
-    // (wordcount: one launch)
-    // (test hooks: CCRDT_WC_LAUNCH_TOKENS, the tokens per launch;
-    // CCRDT_WC_DTAGS, the document tags before the dedupe table is cleared)
-    const uint64_t launch_tok = getenv("CCRDT_WC_LAUNCH_TOKENS") ? strtoull(getenv("CCRDT_WC_LAUNCH_TOKENS"), nullptr, 0) : (1ull << 28);
-    const uint64_t dtags = getenv("CCRDT_WC_DTAGS") ? strtoull(getenv("CCRDT_WC_DTAGS"), nullptr, 0) : (1ull << 24);
-    // (worddocumentcount dedupe entries hold a document tag in 24 bits: at
-    // most 2^23 documents per launch)
-    auto launch_end = [&](uint64_t x0, uint64_t& tk) {
-      uint64_t x1 = x0;
-      tk = 0;
-      while (x1 < nd && (x1 == x0 || !a.wdc || (tk + ntok[x1] <= launch_tok && x1 - x0 < (1ull << 23))))
-        tk += ntok[x1++];
-      return x1;
-    };
-    uint64_t max_rn = 0, max_docs = 0;  // (the document lists are sized once for every launch)
-    for (uint64_t x0 = 0, tk = 0; x0 < nd;) {
-      const uint64_t x1 = launch_end(x0, tk);
-      uint64_t rn = 0;
-      for (uint64_t x = x0; x < x1 && use_dl; ++x) rn += dl_rn[x];
-      max_rn = std::max(max_rn, rn);
-      max_docs = std::max(max_docs, x1 - x0);
-      x0 = x1;
-    }
-    uint64_t d0 = 0;
-    while (d0 < nd) {
-      uint64_t tk = 0;
-      const uint64_t d1 = launch_end(d0, tk);
-      a.n_docs = (int64_t)(d1 - d0);
-      a.doc_key = T.stage[0].as<uint64_t>() + d0;
-      a.doc_off = docs->doc_off + d0;
-      a.tile_ptr = T.stage[4].as<uint64_t>() + d0;
-      a.tile0 = tptr[d0];
-      a.chunk_doc = T.stage[5].as<uint32_t>();
-      a.doc0 = d0;
-      if (a.wdc) {
-        a.group_doc = T.stage[7].as<uint32_t>();
-        a.group_ptr = T.stage[6].as<uint64_t>() + d0;
-        a.group0 = gptr[d0];
-        a.n_groups = gptr[d1] - gptr[d0];
-      }
-      if (a.wdc && dl_on) {
-        CCRDT_TRY(T.dl.ensure(std::max<uint64_t>(max_rn, 1) * 4));
-        CCRDT_TRY(T.dl_cur.ensure(std::max<uint64_t>(max_docs, 1) * 4));
-        CCRDT_HIP(hipMemsetAsync(T.dl_cur.p, 0, (d1 - d0) * 4, e->stream));
-        a.dl = T.dl.as<uint32_t>();
-        a.dl_pre = T.dl_pre.as<uint64_t>() + d0;
-        a.dl_cur = T.dl_cur.as<uint32_t>();
-        a.d_hash = nullptr;
-      } else if (a.wdc) {
-        a.dl = nullptr;
-        // two slots per token (measured: half a slot per token overflowed on
-        // the Zipf corpus and the re-run cost 13 ms); an overflow re-runs the
-        // batch with four times the slots
-        const uint64_t ds = pow2_at_least(std::max<uint64_t>(2 * tk, 1024) * dmul);
-        // not cleared per launch: the launch's document tags lie above every
-        // earlier launch's (WcArgs::d_base), so the old pairs read as free;
-        // only a new buffer, slots never cleared, or spent tags (2^24) clear
-        const uint64_t b0 = T.d_hash.bytes;
-        CCRDT_TRY(T.d_hash.ensure(ds * 8));
-        if (T.d_hash.bytes != b0) T.d_clean = T.d_base = 0;
-        if (T.d_base + (d1 - d0) >= dtags || getenv("CCRDT_WC_DCLEAR")) {  // (diagnostic: every launch)
-          T.d_clean = std::max(T.d_clean, ds);
-          CCRDT_HIP(hipMemsetAsync(T.d_hash.p, 0, T.d_clean * 8, e->stream));
-          T.d_base = 0;
-        } else if (ds > T.d_clean) {
-          CCRDT_HIP(hipMemsetAsync(T.d_hash.as<uint64_t>() + T.d_clean, 0, (ds - T.d_clean) * 8, e->stream));
-          T.d_clean = ds;
-        }
-        a.d_hash = T.d_hash.as<uint64_t>();
-        a.d_mask = ds - 1;
-        a.d_base = T.d_base;
-        T.d_base += d1 - d0;
-      }
-      a.fl_base = a.wdc ? a.group0 : 0;  // (wordcount: one launch)
-      a.dbg = getenv("CCRDT_WC_IDBG") ? atoi(getenv("CCRDT_WC_IDBG")) : 0;
-      CCRDT_TRY(wc_launch_insert(a, tptr[d1] - tptr[d0], e->stream));
-      a.dbg = 0;
-      if (a.wdc && dl_on) CCRDT_TRY(wc_launch_dl(a, d1 - d0, dl_passes, e->stream));
-      d0 = d1;
-    }
+    CCRDT_TRY(wc_insert_launches(e, P, at, a));
     CCRDT_HIP(hipEventRecord(e->evk1, e->stream));
-    uint32_t st[3];
-    CCRDT_TRY(read_status3(e, st));
+    uint32_t st[WC_ST_WORDS];
+    CCRDT_TRY(read_status(e, st, WC_ST_WORDS));
     CCRDT_HIP(hipEventElapsedTime(&e->last_kernel_ms, e->evk0, e->evk1));
-    if (st[0] && attempt < 4) {  // table (or dedupe table) too small, count list full
-      if (st[0] & 1u) slots *= 4;
-      if (st[0] & 2u) dmul *= 4;
-      if (st[0] & 4u) use_cl = false;
-      if (st[0] & 8u) use_dl = false;
+    if (st[WC_ST_GROW] && attempt < 4) {  // nothing is persisted yet: no rollback
+      route[CCRDT_WC_ROUTE_GROW_BITS] |= st[WC_ST_GROW];
+      wc_regrow(at, st[WC_ST_GROW]);
       continue;
     }
-    if (st[0]) {
+    if (st[WC_ST_GROW]) {
       set_error("wc_apply: word table overflow");
       return CCRDT_ENOMEM;
     }
-    // the count list summed into the counts, per bucket of slots
-    if (cl_on) {
-      WcClArgs c{};
-      c.cl = T.cl.as<uint32_t>();
-      c.bcnt = T.cl_bcnt.as<uint32_t>();
-      c.cur = T.cl_small.as<uint32_t>();
-      c.shard_blocks = shard_blocks;
-      c.fl = T.fl.as<uint64_t>();
-      c.tab = fl_tab;
-      c.n_tb = n_tb;
-      c.n_fl = dl_on ? 0 : n_fl;
-      c.bsh = bsh;
-      c.nb = (uint32_t)(slots >> bsh);
-      c.bkt_cnt = T.cl_small.as<uint32_t>() + WC_NSHARD;
-      c.bkt_cur = c.bkt_cnt + WC_CL_NB;
-      c.bkt_off = reinterpret_cast<uint64_t*>(c.bkt_cur + WC_CL_NB);
-      c.t_cnt = a.t_cnt;
-      c.status = a.status;
-      CCRDT_TRY(wc_launch_cl_count(c, e->stream));
-      std::vector<uint64_t> tot;
-      CCRDT_TRY(d2h_at(tot, T.cl_small, (WC_NSHARD + 2 * WC_CL_NB) / 2 + c.nb, 1, e->stream));
-      CCRDT_TRY(T.bkt.ensure(std::max<uint64_t>(tot[0], 1) * 4));
-      c.bkt = T.bkt.as<uint32_t>();
-      CCRDT_TRY(wc_launch_cl_sum(c, e->stream));
-    }
-    // the batch's new words into the arena first (the check list's long
-    // words are compared against a compact, cache-resident copy)
-    a.doc_key = T.stage[0].as<uint64_t>();
-    a.doc_off = docs->doc_off;
-    a.n_docs = (int64_t)nd;
-    a.tile_ptr = T.stage[4].as<uint64_t>();
-    a.tile0 = 0;
-    a.chunk_doc = T.stage[5].as<uint32_t>();
-    a.doc0 = 0;
-    a.group_doc = nullptr;
-    a.arena = T.arena.as<uint8_t>();
-    CCRDT_HIP(hipMemsetAsync((uint64_t*)T.arena_top.p + 1, 0, 8, e->stream));
-    CCRDT_TRY(wc_launch_persist(a, T.arena.as<uint8_t>(), T.arena_top.as<unsigned long long>(), e->stream));
-    // exactness: every token equals its word's identity -- the insert kernel
-    // compared all but the check list's tokens (a full list: every token
-    // again; CCRDT_WC_VERIFY=1 forces that pass)
-    const bool full = (st[1] & 16u) || (getenv("CCRDT_WC_VERIFY") && atoi(getenv("CCRDT_WC_VERIFY")));
-    T.wc_checks = full ? -1 : (int64_t)st[2];
-    if (full) CCRDT_TRY(wc_launch_verify(a, tptr[nd], e->stream));
-    else CCRDT_TRY(wc_launch_check(a, st[2], e->stream));
-    CCRDT_TRY(read_status(e, st));
-    st[1] &= ~16u;
-    if (st[1]) {
-      // the state is unchanged: the new table side is dropped, the arena
-      // top goes back to the words it held
-      const uint64_t back[2] = {arena_used, words_old};
-      CCRDT_TRY(h2d(*e, T.arena_top, back, 16));
-      CCRDT_HIP(hipStreamSynchronize(e->stream));
-      if ((st[1] & 1) && !reseeded) {
+    if (at.cl_on) CCRDT_TRY(wc_count_list_sum(e, P, at, a));
+    CCRDT_TRY(wc_persist_and_check(e, P, a, st));
+    if (st[WC_ST_ERR] & ~WC_CHK_FULL) {  // (a full check list is no error)
+      CCRDT_TRY(wc_rollback(e, P));
+      if ((st[WC_ST_ERR] & WC_ERR_COLLISION) && !at.reseeded) {
         // two distinct words met on one 64-bit hash: the collision depends on
         // the bytes and the seed only, so the batch is re-run once under a
         // new seed (the rehash recomputes every old word's hash)
-        reseeded = true;
+        at.reseeded = true;
         T.wc_seed = wc_next_seed(T.wc_seed);
         continue;
       }
-      set_error(st[1] & 1 ? "wc_apply: 64-bit word hash collision between distinct words (also under a second seed)"
-                          : "wc_apply: token lost (table overflow)");
+      set_error(st[WC_ST_ERR] & WC_ERR_COLLISION
+                    ? "wc_apply: 64-bit word hash collision between distinct words (also under a second seed)"
+                    : "wc_apply: token lost (table overflow)");
       return CCRDT_ERANGE;
     }
     CCRDT_HIP(hipStreamSynchronize(e->stream));
     break;
   }
-  T.tcur = out;
+  route[CCRDT_WC_ROUTE_SLOTS] = (int64_t)at.slots;
+  route[CCRDT_WC_ROUTE_COUNT_LIST] = at.cl_on;
+  route[CCRDT_WC_ROUTE_DOC_LISTS] = at.dl_on;
+  route[CCRDT_WC_ROUTE_DL_PASSES] = at.dl_on ? at.dl_passes : 0;
+  route[CCRDT_WC_ROUTE_LAUNCHES] = (int64_t)P.launches.size();
+  route[CCRDT_WC_ROUTE_RESEEDED] = at.reseeded;
+  T.tcur = 1 - T.tcur;
   e->fresh = false;
   return CCRDT_OK;
+}
+
+// key_ptr, offsets and bytes of a host CSR (documents or words) -> T.kp,
+// T.stage[2], T.stage[3].
+static int wc_upload_csr(ccrdt_engine* e, const uint64_t* key_ptr, const uint64_t* off, uint64_t n,
+                         const uint8_t* bytes, uint64_t n_bytes) {
+  TypeBufs& T = e->tb;
+  CCRDT_TRY(h2d(*e, T.kp, key_ptr, ((uint64_t)e->n_keys + 1) * 8));
+  CCRDT_TRY(h2d(*e, T.stage[2], off, (n + 1) * 8));
+  CCRDT_TRY(h2d(*e, T.stage[3], bytes, n_bytes));
+  return T.stage[3].ensure(8);
 }
 
 int ccrdt_wc_apply(ccrdt_engine* e, const ccrdt_wc_docs* docs) {
@@ -1395,10 +1506,7 @@ int ccrdt_wc_apply(ccrdt_engine* e, const ccrdt_wc_docs* docs) {
     return CCRDT_EINVAL;
   }
   TypeBufs& T = e->tb;
-  CCRDT_TRY(h2d(*e, T.kp, docs->key_ptr, (nk + 1) * 8));
-  CCRDT_TRY(h2d(*e, T.stage[2], docs->doc_off, (nd + 1) * 8));
-  CCRDT_TRY(h2d(*e, T.stage[3], docs->bytes, docs->n_bytes));
-  CCRDT_TRY(T.stage[3].ensure(8));
+  CCRDT_TRY(wc_upload_csr(e, docs->key_ptr, docs->doc_off, nd, docs->bytes, docs->n_bytes));
   ccrdt_wc_docs d{docs->n_docs, T.kp.as<uint64_t>(), T.stage[2].as<uint64_t>(), T.stage[3].as<uint8_t>(),
                   docs->n_bytes};
   return ccrdt_wc_apply_device(e, &d);
@@ -1437,10 +1545,7 @@ static int wc_merge_words(ccrdt_engine* e, int64_t n_words, const uint64_t* key_
   }
   TypeBufs& T = e->tb;
   // words -> device: keys, offsets, bytes, counts
-  CCRDT_TRY(h2d(*e, T.kp, key_ptr, (nk + 1) * 8));
-  CCRDT_TRY(h2d(*e, T.stage[2], word_off, (nw + 1) * 8));
-  CCRDT_TRY(h2d(*e, T.stage[3], bytes, nb));
-  CCRDT_TRY(T.stage[3].ensure(8));
+  CCRDT_TRY(wc_upload_csr(e, key_ptr, word_off, nw, bytes, nb));
   CCRDT_TRY(h2d(*e, T.stage[1], count, nw * 8));
   CCRDT_TRY(T.stage[0].ensure(nw * 8 + 8));
   CCRDT_TRY(wc_launch_doc_key(T.kp.as<uint64_t>(), nk, nw, T.stage[0].as<uint64_t>(), e->stream));
@@ -1461,46 +1566,35 @@ static int wc_merge_core(ccrdt_engine* e, uint64_t nw, const uint64_t* wk, const
   std::vector<uint64_t> top{0, 0};
   if (!e->fresh) CCRDT_TRY(d2h(top, T.arena_top, 2, e->stream));
   const uint64_t words_old = start_empty ? 0 : top[1], arena_used = top[0];
-  if (arena_used + nb > T.arena_cap) {
-    DevBuf grown;
-    const uint64_t cap = std::max<uint64_t>(2 * (arena_used + nb), 4096);
-    CCRDT_TRY(grown.ensure(cap));
-    if (arena_used)
-      CCRDT_HIP(hipMemcpyAsync(grown.p, T.arena.p, arena_used, hipMemcpyDeviceToDevice, e->stream));
-    CCRDT_HIP(hipStreamSynchronize(e->stream));
-    T.arena.release();
-    T.arena = grown;
-    grown.p = nullptr;
-    T.arena_cap = cap;
-  }
-  const int in = T.tcur, out = 1 - T.tcur;
+  CCRDT_TRY(wc_grow_arena(e, arena_used, nb, 0));
   const uint64_t slots = pow2_at_least(2 * (words_old + nw));
+  std::fill_n(T.wc_route, CCRDT_WC_N_ROUTE, 0);
+  T.wc_route[CCRDT_WC_ROUTE_SLOTS] = (int64_t)slots;
   WcArgs a;
   uint32_t st[2];
   for (int attempt = 0;; ++attempt) {
-    CCRDT_TRY(wc_alloc_table(e, out, slots));
-    a = wc_table_args(e, out);
-    if (!start_empty && T.t_slots[in])
-      CCRDT_TRY(wc_launch_rehash(T.t_tab[in].as<WcSlot>(), T.t_meta[in].as<WcMeta>(), T.t_cnt[in].as<unsigned long long>(),
-                                 T.t_slots[in], a, e->stream));
+    T.wc_route[CCRDT_WC_ROUTE_ATTEMPTS] = attempt + 1;
+    CCRDT_TRY(wc_new_table(e, slots, !start_empty, a));
     CCRDT_HIP(hipMemsetAsync(T.status.p, 0, 8, e->stream));
     a.bytes = bytes;
     a.n_bytes = nb;
     CCRDT_TRY(wc_launch_merge(a, wk, wo, wc, nw, 0, e->stream));
     CCRDT_TRY(wc_launch_merge(a, wk, wo, wc, nw, 1, e->stream));
     CCRDT_TRY(read_status(e, st));
-    if (st[1] == 1u && attempt == 0) {  // a hash collision alone: once more under a new seed
+    if (st[WC_ST_ERR] == WC_ERR_COLLISION && attempt == 0) {  // a hash collision alone: once more under a new seed
       T.wc_seed = wc_next_seed(T.wc_seed);
+      T.wc_route[CCRDT_WC_ROUTE_RESEEDED] = 1;
       continue;
     }
     break;
   }
-  if (st[0] || st[1]) {
-    set_error(st[1] & 8   ? "wc_merge: a count < 1 or a key outside [0, n_keys)"
-              : st[1] & 1 ? "wc_merge: 64-bit word hash collision between distinct words"
-              : st[1] & 4 ? "wc_merge: a count would leave int64"
-                          : "wc_merge: word table overflow");
-    return st[1] & 8 ? CCRDT_EINVAL : st[1] & 5 ? CCRDT_ERANGE : CCRDT_ENOMEM;
+  if (st[WC_ST_GROW] || st[WC_ST_ERR]) {
+    const uint32_t err = st[WC_ST_ERR];
+    set_error(err & WC_ERR_INPUT       ? "wc_merge: a count < 1 or a key outside [0, n_keys)"
+              : err & WC_ERR_COLLISION ? "wc_merge: 64-bit word hash collision between distinct words"
+              : err & WC_ERR_RANGE     ? "wc_merge: a count would leave int64"
+                                       : "wc_merge: word table overflow");
+    return err & WC_ERR_INPUT ? CCRDT_EINVAL : err & (WC_ERR_COLLISION | WC_ERR_RANGE) ? CCRDT_ERANGE : CCRDT_ENOMEM;
   }
   // persist appends the new words' bytes at arena_top[0] and counts words in
   // arena_top[1]; a replaced state starts both from zero
@@ -1508,16 +1602,9 @@ static int wc_merge_core(ccrdt_engine* e, uint64_t nw, const uint64_t* wk, const
                            e->stream));
   CCRDT_TRY(wc_launch_persist(a, T.arena.as<uint8_t>(), T.arena_top.as<unsigned long long>(), e->stream));
   CCRDT_HIP(hipStreamSynchronize(e->stream));
-  T.tcur = out;
+  T.tcur = 1 - T.tcur;
   e->fresh = false;
   return CCRDT_OK;
-}
-
-static uint64_t owner_mix(uint64_t z) {  // splitmix64 (cluster.splitmix64)
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 int ccrdt_wc_owner(int64_t n_keys, int64_t n_words, const uint64_t* key_ptr, const uint64_t* word_off,
@@ -1538,7 +1625,7 @@ int ccrdt_wc_owner(int64_t n_keys, int64_t n_words, const uint64_t* key_ptr, con
     for (uint64_t i = key_ptr[k]; i < key_ptr[k + 1]; ++i) {
       uint64_t f = 0xCBF29CE484222325ull;
       for (uint64_t j = word_off[i]; j < word_off[i + 1]; ++j) f = (f ^ bytes[j]) * 0x100000001B3ull;
-      owner[i] = (int32_t)(owner_mix(f ^ ((uint64_t)k * 0x9E3779B97F4A7C15ull)) % (uint64_t)world);
+      owner[i] = (int32_t)(wc_next_seed(f ^ ((uint64_t)k * 0x9E3779B97F4A7C15ull)) % (uint64_t)world);
     }
   }
   return CCRDT_OK;
@@ -1571,8 +1658,7 @@ int ccrdt_wc_partition_device(ccrdt_engine* e, int world, int64_t* d_meta, uint8
   // the owner cursors pack (rows << 40 | bytes) into one 64-bit word, so the
   // rows of one table must stay below 2^24 and its bytes below 2^40
   // (test hook CCRDT_WC_PART_MAX_WORDS lowers the row limit)
-  uint64_t max_words = 1ull << 24;
-  if (const char* s = getenv("CCRDT_WC_PART_MAX_WORDS")) max_words = std::min<uint64_t>(max_words, strtoull(s, nullptr, 0));
+  const uint64_t max_words = std::min<uint64_t>(1ull << 24, WcHooks::part_max_words(1ull << 24));
   if ((uint64_t)nw >= max_words || (uint64_t)nb >= (1ull << 40)) {
     set_error("wc_partition_device: more than 2^24 - 1 words or 2^40 - 1 bytes in one table "
               "(export with ccrdt_wc_export and partition on the host)");
@@ -1633,6 +1719,13 @@ int ccrdt_wc_last_checks(ccrdt_engine* e, int64_t* n_checked) {
   CCRDT_TRY(check_type(e, CCRDT_WORDCOUNT));
   if (!n_checked) return CCRDT_EINVAL;
   *n_checked = e->tb.wc_checks;
+  return CCRDT_OK;
+}
+
+int ccrdt_wc_last_route(ccrdt_engine* e, int64_t* out) {
+  CCRDT_TRY(check_type(e, CCRDT_WORDCOUNT));
+  if (!out) return CCRDT_EINVAL;
+  std::copy(e->tb.wc_route, e->tb.wc_route + CCRDT_WC_N_ROUTE, out);
   return CCRDT_OK;
 }
 

@@ -2075,7 +2075,7 @@ __device__ __forceinline__ uint64_t wc_global_insert_at(const WcArgs& a, uint64_
     sl = (sl + 1) & a.t_mask;
     seen = wc_ld(&a.t[sl].h);
   }
-  atomicOr(&a.status[0], 1u);  // table full
+  atomicOr(&a.status[WC_ST_GROW], WC_GROW_TABLE);  // table full
   return ~0ull;
 }
 __device__ __forceinline__ uint64_t wc_global_insert(const WcArgs& a, uint64_t h, bool& claimed) {
@@ -2107,14 +2107,14 @@ __device__ __forceinline__ bool wc_settle(const WcArgs& a, uint64_t tw0, uint64_
                                           uint64_t sw1, uint64_t sw2) {
   if (wc_ident_len(tw0) > WC_SHORT) return true;
   if (!(sw0 & sw1 & sw2 & WC_MARK)) return true;
-  if (sw0 != tw0 || sw1 != tw1 || sw2 != (WC_MARK | key)) atomicOr(&a.status[1], 1u);
+  if (sw0 != tw0 || sw1 != tw1 || sw2 != (WC_MARK | key)) atomicOr(&a.status[WC_ST_ERR], WC_ERR_COLLISION);
   return false;
 }
 __device__ __forceinline__ void wc_chk_push(const WcArgs& a, uint64_t sl, uint32_t key, uint32_t tl, uint64_t tw0,
                                             uint64_t tw1, uint64_t pos) {
-  const uint32_t i = atomicAdd(&a.status[2], 1u);
+  const uint32_t i = atomicAdd(&a.status[WC_ST_CHECKS], 1u);
   if (i >= a.chk_cap) {  // list full: the verify pass checks every token instead
-    atomicOr(&a.status[1], 16u);
+    atomicOr(&a.status[WC_ST_ERR], WC_CHK_FULL);
     return;
   }
   WcChk* r = a.chk + i;
@@ -2150,7 +2150,7 @@ __device__ __forceinline__ bool wc_doc_first(const WcArgs& a, uint64_t g, uint64
     if (prev == seen) return true;
     seen = prev;  // (this slot again, with what it holds)
   }
-  atomicOr(&a.status[0], 2u);
+  atomicOr(&a.status[WC_ST_GROW], WC_GROW_DEDUPE);
   return false;
 }
 
@@ -2206,7 +2206,7 @@ __device__ __forceinline__ void wc_cl_push(const WcArgs& a, bool need, uint32_t 
     if (lane_id() == 0) {
       if (blk != ~0u) a.cl_bcnt[blk] = fill;
       idx = atomicAdd(&a.cl_cur[shard], 1u);
-      if (idx >= a.cl_shard_blocks) atomicOr(&a.status[0], 4u);  // list full: the batch is re-run with adds
+      if (idx >= a.cl_shard_blocks) atomicOr(&a.status[WC_ST_GROW], WC_GROW_COUNT_LIST);  // list full: the batch is re-run with adds
     }
     idx = __builtin_amdgcn_readfirstlane(idx);
     blk = idx < a.cl_shard_blocks ? shard * a.cl_shard_blocks + idx : ~0u;
@@ -2225,7 +2225,7 @@ __device__ __forceinline__ void wc_cl_push(const WcArgs& a, bool need, uint32_t 
 // of the document (a document never has more pairs than tokens: an LDS entry
 // stands for at least one token, a miss for one; a block left early loses less
 // than 64 of its WC_DL_BLK entries); past it the batch is re-run with the
-// dedupe table (status 8).
+// dedupe table (WC_GROW_DOC_LIST).
 __device__ __forceinline__ void wc_dl_push(const WcArgs& a, bool need, uint32_t gs, uint64_t doc, uint32_t& dpos,
                                            uint32_t& dend) {
   const uint64_t m = ballot(need);
@@ -2238,7 +2238,7 @@ __device__ __forceinline__ void wc_dl_push(const WcArgs& a, bool need, uint32_t 
     if (lane_id() == 0) base = atomicAdd(&a.dl_cur[doc], WC_DL_BLK);
     base = __builtin_amdgcn_readfirstlane(base);
     if ((uint64_t)base + WC_DL_BLK > a.dl_pre[doc + 1] - a.dl_pre[doc]) {
-      if (lane_id() == 0) atomicOr(&a.status[0], 8u);
+      if (lane_id() == 0) atomicOr(&a.status[WC_ST_GROW], WC_GROW_DOC_LIST);
       dpos = dend = 0;
       return;
     }
@@ -2651,7 +2651,7 @@ __global__ __launch_bounds__(256) void wc_check_kernel(WcArgs a, uint32_t n) {
   const WcChk r = a.chk[i];
   const WcSlot s = a.t[r.slot];
   if (r.a & WC_MARK) {  // a short word: its identity
-    if (s.w0 != r.a || s.w1 != r.b || s.w2 != (WC_MARK | r.key)) atomicOr(&a.status[1], 1u);
+    if (s.w0 != r.a || s.w1 != r.b || s.w2 != (WC_MARK | r.key)) atomicOr(&a.status[WC_ST_ERR], WC_ERR_COLLISION);
     return;
   }
   const WcMeta m = a.tm[r.slot];
@@ -2670,7 +2670,7 @@ __global__ __launch_bounds__(256) void wc_check_kernel(WcArgs a, uint32_t n) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) eq = eq && x[j] == y[j];
   }
-  if (!eq) atomicOr(&a.status[1], 1u);
+  if (!eq) atomicOr(&a.status[WC_ST_ERR], WC_ERR_COLLISION);
 }
 
 // Fallback when the check list filled up: every token of the batch is
@@ -2715,18 +2715,18 @@ __global__ __launch_bounds__(64 * WAVES) void wc_verify_kernel(WcArgs a) {
         uint64_t sl = h & a.t_mask;
         while (a.t[sl].h != h && a.t[sl].h != 0ull) sl = (sl + 1) & a.t_mask;
         if (a.t[sl].h != h) {
-          atomicOr(&a.status[1], 2u);  // lost token (table overflow)
+          atomicOr(&a.status[WC_ST_ERR], WC_ERR_LOST);  // lost token (table overflow)
           continue;
         }
         if (tl <= WC_SHORT) {
-          if (a.t[sl].w0 != tw0 || a.t[sl].w1 != tw1 || a.t[sl].w2 != (WC_MARK | key)) atomicOr(&a.status[1], 1u);
+          if (a.t[sl].w0 != tw0 || a.t[sl].w1 != tw1 || a.t[sl].w2 != (WC_MARK | key)) atomicOr(&a.status[WC_ST_ERR], WC_ERR_COLLISION);
           continue;
         }
         const WcMeta m = a.tm[sl];
         bool eq = m.key == key && m.len == tl;
         const uint8_t* rep = (m.ref & WC_REF_BATCH) ? a.bytes + (m.ref & ~WC_REF_BATCH) : a.arena + m.ref;
         for (uint32_t j = 0; eq && j < tl; ++j) eq = rep[j] == v.at(s + j);
-        if (!eq) atomicOr(&a.status[1], 1u);
+        if (!eq) atomicOr(&a.status[WC_ST_ERR], WC_ERR_COLLISION);
       }
     }
   }
@@ -2971,7 +2971,7 @@ __global__ void wc_merge_kernel(WcArgs a, const uint64_t* wkey, const uint64_t* 
   const uint64_t h = wc_hkey(a, wc_hash_bytes(a.bytes + s, len), key, len);
   if (!verify) {
     if (cnt[i] < 1 || key >= (uint64_t)a.n_keys) {  // a map entry counts at least one token
-      atomicOr(&a.status[1], 8u);
+      atomicOr(&a.status[WC_ST_ERR], WC_ERR_INPUT);
       return;
     }
     bool claimed;
@@ -2984,7 +2984,7 @@ __global__ void wc_merge_kernel(WcArgs a, const uint64_t* wkey, const uint64_t* 
       }
       const unsigned long long c = (unsigned long long)cnt[i];
       const unsigned long long o = atomicAdd(&a.t_cnt[g], c);
-      if (o + c > 0x7FFFFFFFFFFFFFFFull) atomicOr(&a.status[1], 4u);  // leaves int64
+      if (o + c > 0x7FFFFFFFFFFFFFFFull) atomicOr(&a.status[WC_ST_ERR], WC_ERR_RANGE);  // leaves int64
     }
     return;
   }
@@ -2992,14 +2992,14 @@ __global__ void wc_merge_kernel(WcArgs a, const uint64_t* wkey, const uint64_t* 
   for (uint64_t probe = 0; probe <= a.t_mask && a.t[sl].h != h && a.t[sl].h != 0ull; ++probe)
     sl = (sl + 1) & a.t_mask;
   if (a.t[sl].h != h) {
-    atomicOr(&a.status[1], 2u);
+    atomicOr(&a.status[WC_ST_ERR], WC_ERR_LOST);
     return;
   }
   const WcMeta m = a.tm[sl];
   const uint8_t* rep = !(m.ref & WC_REF_BATCH) ? a.arena + m.ref : a.bytes + (m.ref & ~WC_REF_BATCH);
   bool eq = m.key == key && m.len == len;
   for (uint32_t j = 0; eq && j < len; ++j) eq = rep[j] == a.bytes[s + j];
-  if (!eq) atomicOr(&a.status[1], 1u);
+  if (!eq) atomicOr(&a.status[WC_ST_ERR], WC_ERR_COLLISION);
 }
 
 // ---- the key-sharded histogram's exchange, on the device (cluster.py):

@@ -181,6 +181,19 @@ struct WcChk {
   uint64_t b;
 };
 
+// The wordcount status block (WcArgs::status): three words, cleared before
+// the kernels that write them and read back after.
+enum : uint32_t { WC_ST_GROW = 0, WC_ST_ERR = 1, WC_ST_CHECKS = 2, WC_ST_WORDS = 3 };
+// word WC_ST_GROW, insert kernel: a structure of this attempt was full (the
+// batch is re-run; the same values as CCRDT_WC_GROW_* of include/ccrdt.h)
+enum : uint32_t { WC_GROW_TABLE = 1u, WC_GROW_DEDUPE = 2u, WC_GROW_COUNT_LIST = 4u, WC_GROW_DOC_LIST = 8u };
+// word WC_ST_ERR, insert / check / verify / merge kernels: two distinct words
+// on one 64-bit hash; a token (merge: a word) without a slot; a count leaves
+// int64 (merge); a count < 1 or a key outside [0, n_keys) (merge); the check
+// list was full (insert: the batch is verified token by token, no error)
+enum : uint32_t { WC_ERR_COLLISION = 1u, WC_ERR_LOST = 2u, WC_ERR_RANGE = 4u, WC_ERR_INPUT = 8u, WC_CHK_FULL = 16u };
+// word WC_ST_CHECKS: the records the insert kernel put on the check list
+
 struct WcArgs {
   int64_t n_keys;
   int64_t n_docs;
@@ -218,7 +231,7 @@ struct WcArgs {
   uint32_t* dl;              // regions, one per document of the launch: its tokens' worth of entries
   const uint64_t* dl_pre;    // [launch docs + 1] token prefix: region of d = [dl_pre[d], dl_pre[d + 1]) - dl_pre[0]
   uint32_t* dl_cur;          // [launch docs] entries appended
-  uint32_t* status;          // [0] table overflow (1) | dedupe table (2) | count list full (4) | document list full (8), [1] hash collision | token lost | check list full (16), [2] check records
+  uint32_t* status;          // WC_ST_WORDS words (WC_ST_*, above)
   WcChk* chk;                // the check list (wc_check_kernel), chk_cap records
   uint32_t chk_cap;
   // The count list (wc_cl_*): the insert kernel's count adds, summed after

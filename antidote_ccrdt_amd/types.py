@@ -242,6 +242,14 @@ class LeaderboardEngine(_Engine):
 
 
 # ------------------------------------------------ wordcount / worddocumentcount
+# slots of WordcountEngine.last_route() and the bits of its GROW_BITS slot
+# (include/ccrdt.h, CCRDT_WC_ROUTE_* / CCRDT_WC_GROW_*)
+(WC_ROUTE_ATTEMPTS, WC_ROUTE_SLOTS, WC_ROUTE_COUNT_LIST, WC_ROUTE_DOC_LISTS, WC_ROUTE_DL_PASSES,
+ WC_ROUTE_LAUNCHES, WC_ROUTE_RESEEDED, WC_ROUTE_GROW_BITS) = range(8)
+WC_N_ROUTE = 8
+WC_GROW_TABLE, WC_GROW_DEDUPE, WC_GROW_COUNT_LIST, WC_GROW_DOC_LIST = 1, 2, 4, 8
+
+
 class WordcountEngine(_Engine):
     """antidote_ccrdt_wordcount (src/antidote_ccrdt_wordcount.erl)."""
     TYPE = _lib.WORDCOUNT
@@ -281,6 +289,14 @@ class WordcountEngine(_Engine):
         n = C.c_int64()
         check(lib.ccrdt_wc_last_checks(self.h, C.byref(n)), "wc_last_checks")
         return int(n.value)
+
+    def last_route(self) -> list[int]:
+        """The route of the last batch, indexed by WC_ROUTE_*: attempts, table
+        slots, count list / document lists used, list passes, insert launches,
+        reseeded, and the WC_GROW_* bits of the attempts that were re-run."""
+        r = (C.c_int64 * WC_N_ROUTE)()
+        check(lib.ccrdt_wc_last_route(self.h, r), "wc_last_route")
+        return [int(x) for x in r]
 
     def export(self):
         """(key_ptr, word_off, word_bytes, count): words sorted by bytes per key."""

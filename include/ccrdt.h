@@ -532,6 +532,32 @@ int ccrdt_wc_sizes(ccrdt_engine* e, int64_t* n_words, int64_t* n_bytes);
  * identity was not yet visible), or -1 when the batch was verified token by
  * token (the list filled up). */
 int ccrdt_wc_last_checks(ccrdt_engine* e, int64_t* n_checked);
+/* The route of the last ccrdt_wc_apply(_device) (every fallback is exact, so
+ * only this record says which one a batch took): runs of the attempt loop,
+ * the committed one included; word-table slots of the committed attempt; 1 if
+ * it summed the LDS misses' counts through the count list (0: device adds);
+ * 1 if it used worddocumentcount's document lists (0: the dedupe table); the
+ * bitmap passes of the document lists (0 without them); its insert launches;
+ * 1 if the batch was re-run under a new word-hash seed; the OR of the table
+ * status (CCRDT_WC_GROW_*) over the attempts that were re-run. */
+#define CCRDT_WC_ROUTE_ATTEMPTS 0
+#define CCRDT_WC_ROUTE_SLOTS 1
+#define CCRDT_WC_ROUTE_COUNT_LIST 2
+#define CCRDT_WC_ROUTE_DOC_LISTS 3
+#define CCRDT_WC_ROUTE_DL_PASSES 4
+#define CCRDT_WC_ROUTE_LAUNCHES 5
+#define CCRDT_WC_ROUTE_RESEEDED 6
+#define CCRDT_WC_ROUTE_GROW_BITS 7
+#define CCRDT_WC_N_ROUTE 8
+/* Bits of CCRDT_WC_ROUTE_GROW_BITS: the word table, the dedupe table, the
+ * count list or a document list was full. */
+#define CCRDT_WC_GROW_TABLE 1
+#define CCRDT_WC_GROW_DEDUPE 2
+#define CCRDT_WC_GROW_COUNT_LIST 4
+#define CCRDT_WC_GROW_DOC_LIST 8
+/* out[CCRDT_WC_N_ROUTE]: the slots above.  ccrdt_wc_merge / _import /
+ * _merge_device fill ATTEMPTS, SLOTS and RESEEDED and leave the rest 0. */
+int ccrdt_wc_last_route(ccrdt_engine* e, int64_t* out);
 /* value/1 (:47-48) = the map word -> count; per key, words sorted by bytes
  * (Erlang binary order): key_ptr[n_keys+1] over words, word_off[n_words+1]
  * over word_bytes. */

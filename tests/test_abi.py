@@ -48,6 +48,21 @@ def test_trmv_tier_and_slot_names_match_the_header():
     assert engine.TRMV_TIER_LAST == engine.TRMV_TIER_HBM == engine.TRMV_N_TIERS - 1
 
 
+def test_wc_route_names_match_the_header():
+    # the route slots and grow bits include/ccrdt.h names, mirrored in types.py
+    from antidote_ccrdt_amd import types
+    txt = open(os.path.join(ROOT, "include", "ccrdt.h")).read()
+    names = dict(re.findall(r"^#define CCRDT_(WC_(?:ROUTE|GROW|N)_[A-Z0-9_]+) +(\d+)\b", txt, flags=re.M))
+    assert {"WC_ROUTE_ATTEMPTS", "WC_ROUTE_SLOTS", "WC_ROUTE_COUNT_LIST", "WC_ROUTE_DOC_LISTS",
+            "WC_ROUTE_DL_PASSES", "WC_ROUTE_LAUNCHES", "WC_ROUTE_RESEEDED", "WC_ROUTE_GROW_BITS",
+            "WC_N_ROUTE", "WC_GROW_TABLE", "WC_GROW_COUNT_LIST"} <= set(names), sorted(names)
+    assert len(names) == 13, sorted(names)
+    for name, value in names.items():
+        assert getattr(types, name) == int(value), name
+    assert int(names["WC_N_ROUTE"]) == 8
+    assert sorted(int(v) for n, v in names.items() if n.startswith("WC_ROUTE_")) == list(range(8))
+
+
 def test_registry():
     # antidote_ccrdt:is_type/1 and generates_extra_operations/1 (antidote_ccrdt.erl:61-65)
     assert [_lib.lib.ccrdt_is_type(t) for t in range(-1, 7)] == [0, 1, 1, 1, 1, 1, 1, 0]

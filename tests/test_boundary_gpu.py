@@ -19,7 +19,8 @@ import pytest
 import oracle as orc
 from antidote_ccrdt_amd import _lib
 from antidote_ccrdt_amd.engine import TRMV_MAX_PLAYERS, TopkRmvEngine, TrmvBatch, TrmvExtra, gen_trmv
-from antidote_ccrdt_amd.types import WordcountEngine, WordDocumentCountEngine
+from antidote_ccrdt_amd.types import (WC_ROUTE_ATTEMPTS, WC_ROUTE_RESEEDED, WordcountEngine,
+                                      WordDocumentCountEngine)
 
 pytestmark = pytest.mark.gpu
 
@@ -281,16 +282,24 @@ def test_wc_reseed_on_hash_collision(gpu, E, monkeypatch):
     e, o = E(2), orc.WcOracle(2, E is WordDocumentCountEngine)
     e.apply_docs(docs)
     o.apply_docs(docs)
+    r = e.last_route()
+    print("route first", r)
+    assert r[WC_ROUTE_RESEEDED] == 1 and r[WC_ROUTE_ATTEMPTS] == 2
     for x, y in zip(e.export(), o.export()):
         assert np.array_equal(x, y)
     # the next batch runs under the new seed (the rehash recomputes the words)
     more = [[b"abf abc zz"], [b"qq qr abc"]]
     e.apply_docs(more)
     o.apply_docs(more)
+    r = e.last_route()
+    print("route second", r)
+    assert r[WC_ROUTE_RESEEDED] == 0
     for x, y in zip(e.export(), o.export()):
         assert np.array_equal(x, y)
     # the (word, count) import path takes the same retry
     f = E(2)
     maps = [{b"aa": 3, b"ab": 4, b"ac": 5}, {b"aa": 1}]
     f.import_state(*_import(f, maps))
+    print("route import", f.last_route())
+    assert f.last_route()[WC_ROUTE_RESEEDED] == 1
     assert [f.value(k) for k in range(2)] == maps

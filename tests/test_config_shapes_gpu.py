@@ -25,8 +25,9 @@ import pytest
 
 import oracle as orc
 from antidote_ccrdt_amd import _lib
-from antidote_ccrdt_amd.types import (AverageEngine, DeviceBatch, LeaderboardEngine, TopkEngine,
-                                      WordcountEngine, WordDocumentCountEngine)
+from antidote_ccrdt_amd.types import (WC_GROW_TABLE, WC_ROUTE_ATTEMPTS, WC_ROUTE_GROW_BITS, AverageEngine,
+                                      DeviceBatch, LeaderboardEngine, TopkEngine, WordcountEngine,
+                                      WordDocumentCountEngine)
 
 pytestmark = pytest.mark.gpu
 
@@ -162,6 +163,10 @@ def test_wordcount_config4_single_engine(gpu, wdc, slots, monkeypatch):
     d = DeviceBatch(WC_DOCS, key_ptr=np.array([0, WC_DOCS], np.uint64), doc_off=off, bytes=b)
     e.apply_device(d, b.shape[0])
     d.close()
+    if slots:
+        r = e.last_route()
+        print("route", r)
+        assert r[WC_ROUTE_ATTEMPTS] >= 2 and r[WC_ROUTE_GROW_BITS] & WC_GROW_TABLE
     want = _wc_oracle(wdc)
     assert int(want[0][-1]) > 500_000  # the 1e6-vocabulary table regime
     assert _same_export(e.export(), want)

@@ -5,6 +5,7 @@ import pytest
 
 import oracle as orc
 from antidote_ccrdt_amd import _lib
+from antidote_ccrdt_amd import types as wct
 from antidote_ccrdt_amd.types import (AverageEngine, LeaderboardEngine, TopkEngine,
                                       WordcountEngine, WordDocumentCountEngine, _csr)
 from types_helpers import FIX, avg_fixture_ops, lb_batch, lb_state_key, run_lb_fixture
@@ -273,6 +274,26 @@ def test_wordcount_lds_overflow_path(gpu):
         assert e.value() == o.value()
 
 
+@pytest.mark.parametrize("wdc", [False, True])
+def test_wordcount_table_regrow(gpu, wdc, monkeypatch):
+    """A word table that starts too small for the batch (CCRDT_WC_SLOTS=1024
+    against 3,000 distinct words) reports table-full, and the batch is re-run
+    on a table four times larger until it fits: vs the oracle."""
+    monkeypatch.setenv("CCRDT_WC_SLOTS", "1024")
+    docs = [[b" ".join(b"x%05d" % i for i in range(3000))]]
+    E = WordDocumentCountEngine if wdc else WordcountEngine
+    e, o = E(1), orc.WcOracle(1, wdc)
+    e.apply_docs(docs)
+    o.apply_docs(docs)
+    r = e.last_route()
+    print("route", wdc, r)
+    assert r[wct.WC_ROUTE_ATTEMPTS] >= 2
+    assert r[wct.WC_ROUTE_GROW_BITS] & wct.WC_GROW_TABLE
+    assert r[wct.WC_ROUTE_SLOTS] >= 4096
+    for x, y in zip(e.export(), o.export()):
+        assert np.array_equal(x, y)
+
+
 def _identity_docs(rng):
     """Words around the identity boundary (14 / 15 / 16 bytes), words that
     differ only past byte 7 or only in length, zero bytes inside and at the
@@ -330,6 +351,13 @@ def test_wordcount_count_list(gpu, wdc, mode, monkeypatch):
     for kp in (np.array([0, 4, 10, n_docs], np.uint64), np.array([0, 8, 9, n_docs], np.uint64)):
         e.apply(kp, off, b)
         o.apply(kp, off, b)
+        r = e.last_route()
+        print("route", mode, wdc, r)
+        if mode == "list_full":
+            assert r[wct.WC_ROUTE_ATTEMPTS] >= 2 and r[wct.WC_ROUTE_COUNT_LIST] == 0
+            assert r[wct.WC_ROUTE_GROW_BITS] & wct.WC_GROW_COUNT_LIST
+        else:
+            assert r[wct.WC_ROUTE_ATTEMPTS] == 1 and r[wct.WC_ROUTE_COUNT_LIST] == (mode == "list")
         for x, y in zip(e.export(), o.export()):
             assert np.array_equal(x, y)
 
@@ -380,13 +408,19 @@ def test_wdc_dedupe_tags_across_launches(gpu, monkeypatch, dtags):
     rng = np.random.default_rng(5)
     vocab = [b"w%d" % i for i in range(400)]
     e, o = WordDocumentCountEngine(3), orc.WcOracle(3, True)
+    launches = []
     for _ in range(4):
         docs = [[b" ".join(vocab[i] for i in rng.integers(0, len(vocab), int(rng.integers(0, 2500))))
                  for _ in range(int(rng.integers(0, 6)))] for _ in range(3)]
         e.apply_docs(docs)
         o.apply_docs(docs)
+        r = e.last_route()
+        print("route", dtags, r)
+        assert r[wct.WC_ROUTE_DOC_LISTS] == 0
+        launches.append(r[wct.WC_ROUTE_LAUNCHES])
         for x, y in zip(e.export(), o.export()):
             assert np.array_equal(x, y)
+    assert max(launches) > 1, launches
 
 
 @pytest.mark.parametrize("slots", [None, str(1 << 22)])
@@ -411,6 +445,12 @@ def test_wdc_document_lists(gpu, monkeypatch, slots, launch_tokens):
                  for _ in range(int(rng.integers(0, 5)))] for _ in range(4)]
         e.apply_docs(docs)
         o.apply_docs(docs)
+        r = e.last_route()
+        print("route", slots, launch_tokens, r)
+        assert r[wct.WC_ROUTE_DOC_LISTS] == 1
+        assert r[wct.WC_ROUTE_DL_PASSES] == (4 if slots else 1)
+        many =bool(launch_tokens) and sum(len(d) > 0 for ds in docs for d in ds) > 1
+        assert (r[wct.WC_ROUTE_LAUNCHES] > 1) == many
         for x, y in zip(e.export(), o.export()):
             assert np.array_equal(x, y)
 
