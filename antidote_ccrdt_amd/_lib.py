@@ -178,6 +178,9 @@ SIGNATURES = {
     "ccrdt_wc_last_checks": (INT, [P, C.POINTER(I64)]),
     "ccrdt_wc_last_route": (INT, [P, C.POINTER(I64)]),
     "ccrdt_wc_export": (INT, [P, P, P, P, P]),
+    "ccrdt_wc_value_size": (INT, [P, I64, P, C.POINTER(I64), C.POINTER(I64)]),
+    "ccrdt_wc_value": (INT, [P, I64, P, P, P, P, P]),
+    "ccrdt_wc_value_device": (INT, [P, I64, P, P, P, P, P, I64, I64, P]),
     "ccrdt_lb_extras_device": (INT, [P, P, I64, P]),
     "ccrdt_lb_value_size": (INT, [P, I64, P, C.POINTER(I64)]),
     "ccrdt_lb_value": (INT, [P, I64, P, P, P, P]),

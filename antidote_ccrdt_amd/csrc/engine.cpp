@@ -97,6 +97,7 @@ void ccrdt_engine::release_all() {
                     &val_score, &st_kp,
                     &st_kind, &st_id, &st_score, &st_dc, &st_ts, &st_rvc, &st_out_kind, &st_out_vc})
     d->release();
+  wcv.release();
   release_types();
 }
 

@@ -44,6 +44,21 @@ struct TypeBufs {
   DevBuf hb_off, hb_cap, hb_a, hb_b, hb_c, hb_d;
 };
 
+// Scratch of the keyed value/1 of wordcount / worddocumentcount
+// (wc_value_kernels.hip), grown on demand; a read changes nothing else.
+struct WcValBufs {
+  DevBuf map, cnt, bytes, cur, tot, caps, part;  // key map, per-position words / bytes / cursors, totals, scan scratch
+  DevBuf tiles;                                  // the tile list of the workgroup and large classes (count first)
+  DevBuf idx[2], pre[2];                         // slot indices and sort prefixes, ping-pong sides of the merge passes
+  DevBuf len, off;                               // lengths in sorted order and their exclusive scan
+  DevBuf keys, kptr, woff, wbytes, count;        // the host variant's uploaded keys and device-side result
+  void release() {
+    for (DevBuf* d : {&map, &cnt, &bytes, &cur, &tot, &caps, &part, &tiles, &idx[0], &idx[1], &pre[0], &pre[1], &len,
+                      &off, &keys, &kptr, &woff, &wbytes, &count})
+      d->release();
+  }
+};
+
 }  // namespace ccrdt
 
 struct ccrdt_engine {
@@ -115,6 +130,7 @@ struct ccrdt_engine {
 
   // other types
   ccrdt::TypeBufs tb;
+  ccrdt::WcValBufs wcv;
 
   ccrdt::TrmvSide trmv_side(int ms, int ds) const;
   ccrdt::TrmvSide trmv_cur() const { return trmv_side(mcur, cur); }

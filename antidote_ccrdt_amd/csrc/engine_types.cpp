@@ -1172,6 +1172,10 @@ static int wc_plan_sizes(ccrdt_engine* e, WcPlan& P) {
   // resident in the 256 MiB Infinity Cache; a batch with more overflows it and
   // is re-run on a table four times larger)
   P.slots0 = WcHooks::slots(pow2_at_least(2 * (P.words_old + std::min<uint64_t>(P.tokens, 1ull << 20))));
+  // (the words already held are rehashed into the first table before the
+  // batch is inserted: a hook value they do not fit in would never leave
+  // wc_rehash_kernel's probe loop, so it is raised to twice their number)
+  P.slots0 = std::max<uint64_t>(P.slots0, pow2_at_least(2 * P.words_old));
   // the check list: tokens whose identity the insert kernel leaves open
   // (words of more than WC_SHORT bytes; slots whose identity was not yet
   // visible); a batch that fills it is verified token by token instead

@@ -248,6 +248,18 @@ class LeaderboardEngine(_Engine):
  WC_ROUTE_LAUNCHES, WC_ROUTE_RESEEDED, WC_ROUTE_GROW_BITS) = range(8)
 WC_N_ROUTE = 8
 WC_GROW_TABLE, WC_GROW_DEDUPE, WC_GROW_COUNT_LIST, WC_GROW_DOC_LIST = 1, 2, 4, 8
+# size classes of values() by the words of a key (csrc/wc_value_kernels.hpp):
+# a wave ranks up to WCV_WAVE_MAX words, a workgroup sorts up to WCV_TILE, a
+# larger key is sorted in tiles of WCV_TILE and merged in wcv_passes() passes
+WCV_WAVE_MAX, WCV_TILE = 128, 4096
+
+
+def wcv_passes(words: int) -> int:
+    """Merge passes a key of `words` words takes (wc_value_kernels.hpp)."""
+    p = 0
+    while (WCV_TILE << p) < words:
+        p += 1
+    return p
 
 
 class WordcountEngine(_Engine):
@@ -323,11 +335,43 @@ class WordcountEngine(_Engine):
         """from_binary/1 analogue: the maps := the given words and counts."""
         self._words(lib.ccrdt_wc_import, key_ptr, word_off, word_bytes, count, "wc_import")
 
+    def values(self, keys=None, n: int | None = None):
+        """value/1 of `keys` (key indices in any order, repeats allowed; None:
+        keys 0 .. n - 1, n = every key by default) read on the device:
+        (key_ptr, word_off, word_bytes, count) in the layout of export(),
+        segment i = the words of keys[i] in Erlang binary order.  Three scans
+        of the word table (one to size the arrays, two in the read) whatever
+        the list holds; only the listed keys' words are ordered and copied."""
+        if keys is None:
+            n, kp = self.n_keys if n is None else int(n), None
+        else:
+            keys = np.asarray(keys)
+            if keys.dtype != np.uint64:  # (a negative index wraps and is refused as out of range)
+                keys = keys.astype(np.int64).astype(np.uint64)
+            keys = _c(keys, np.uint64).reshape(-1)
+            n, kp = int(keys.shape[0]), ptr(keys)
+        nw, nb = C.c_int64(), C.c_int64()
+        check(lib.ccrdt_wc_value_size(self.h, n, kp, C.byref(nw), C.byref(nb)), "wc_value_size")
+        nw, nb = int(nw.value), int(nb.value)
+        p, wo = np.zeros(n + 1, np.uint64), np.zeros(nw + 1, np.uint64)
+        wb, cnt = np.zeros(max(nb, 1), np.uint8), np.zeros(max(nw, 1), np.int64)
+        check(lib.ccrdt_wc_value(self.h, n, kp, ptr(p), ptr(wo), ptr(wb), ptr(cnt)), "wc_value")
+        return p, wo, wb[:nb], cnt[:nw]
+
+    def values_device(self, n: int, d_keys: int | None, d_key_ptr: int, d_word_off: int, d_word_bytes: int,
+                      d_count: int, cap_words: int, cap_bytes: int, d_totals: int) -> None:
+        """Enqueue values() of n keys (device uint64[n] at d_keys, None: key i
+        = i) into device arrays: d_totals int64[2] (words, bytes) and
+        d_key_ptr uint64[n + 1] always complete; d_word_off uint64[cap_words +
+        1], d_count int64[cap_words] and d_word_bytes uint8[cap_bytes] written
+        for every key that fits whole below both capacities."""
+        check(lib.ccrdt_wc_value_device(self.h, n, d_keys, d_key_ptr, d_word_off, d_word_bytes, d_count,
+                                        cap_words, cap_bytes, d_totals), "values_device")
+
     def value(self, k: int = 0) -> dict[bytes, int]:
         """value/1 of key k: the map word -> count."""
-        kp, wo, wb, cnt = self.export()
-        return {bytes(wb[int(wo[i]):int(wo[i + 1])]): int(cnt[i])
-                for i in range(int(kp[k]), int(kp[k + 1]))}
+        _, wo, wb, cnt = self.values([k])
+        return {bytes(wb[int(wo[i]):int(wo[i + 1])]): int(cnt[i]) for i in range(cnt.shape[0])}
 
 
 class WordDocumentCountEngine(WordcountEngine):

@@ -563,6 +563,40 @@ int ccrdt_wc_last_route(ccrdt_engine* e, int64_t* out);
  * over word_bytes. */
 int ccrdt_wc_export(ccrdt_engine* e, uint64_t* key_ptr, uint64_t* word_off, uint8_t* word_bytes,
                     int64_t* count);
+/* value/1 of n keys at once, read on the device (both word types).  keys[i]
+ * is a key index, in any order, repeats allowed (each occurrence gets its own
+ * copy of the segment); keys == NULL means key i = i (n <= n_keys).  The
+ * layout is ccrdt_wc_export's restricted to the list: key_ptr[n + 1] over
+ * words, word_off[n_words + 1] over word_bytes, count[n_words]; inside a
+ * segment the words are in Erlang binary order (unsigned bytewise, a proper
+ * prefix first; the empty word first of all).  The table has no
+ * per-key index, so whatever n is a call scans the whole word table: once in
+ * _value_size, twice in _value and _value_device (count, then scatter); only
+ * the listed keys' words are ordered and only they cross to the host.  A fresh or reset engine gives all-empty segments
+ * and reads no state.  A read never changes the engine's state.
+ * Host variants: _value_size gives the word and byte counts to size the
+ * outputs for; a key index outside [0, n_keys), n < 0, n > n_keys without a
+ * list or a NULL output is CCRDT_EINVAL (nothing written, the engine stays
+ * usable); n == 0 is valid (key_ptr[0] = 0, word_off[0] = 0).
+ * _value_device: every pointer is device memory; the call is enqueued on the
+ * engine stream (after a preceding apply_device) and does not wait for the
+ * device (except where its scratch has to grow).  d_word_off holds
+ * cap_words + 1 entries, d_count cap_words, d_word_bytes cap_bytes.
+ * d_totals[0 .. 1] = the true word and byte totals and d_key_ptr[0 .. n]
+ * (d_key_ptr[n] = the true word total) are always written in full.  A key is
+ * written only when it fits as a whole: its last word lies below cap_words
+ * (d_key_ptr[i + 1] <= cap_words) and its last byte below cap_bytes; the keys
+ * that fit are a prefix of the list, their d_word_off entries (up to and
+ * including the end of the last one) are the true offsets, and nothing at or
+ * past either capacity is touched.  d_word_off[0] = 0 is always written.  An
+ * out-of-range key yields an empty segment and reads nothing.  Scratch on the
+ * engine grows with min(cap_words, table slots x n). */
+int ccrdt_wc_value_size(ccrdt_engine* e, int64_t n, const uint64_t* keys, int64_t* n_words, int64_t* n_bytes);
+int ccrdt_wc_value(ccrdt_engine* e, int64_t n, const uint64_t* keys, uint64_t* key_ptr, uint64_t* word_off,
+                   uint8_t* word_bytes, int64_t* count);
+int ccrdt_wc_value_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys, uint64_t* d_key_ptr,
+                          uint64_t* d_word_off, uint8_t* d_word_bytes, int64_t* d_count, int64_t cap_words,
+                          int64_t cap_bytes, int64_t* d_totals);
 /* The key-sharded histogram's exchange on the device (cluster.py): every
  * word of the maps, grouped by owner rank (the ccrdt_wc_owner function),
  * into device rows d_meta[n_words][3] = {key, length, count} and their bytes
