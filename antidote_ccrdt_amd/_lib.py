@@ -29,6 +29,12 @@ INT = C.c_int
 
 
 class CcrdtError(RuntimeError):
+    """A CCRDT_* return code other than OK (`code`).  Raised by
+    TopkRmvEngine.compact_device, it carries `totals` = (ops, clock rows) of
+    the compacted batch as far as the call got to set them: with ENOMEM the
+    true totals, to size the outputs by."""
+    totals = None
+
     def __init__(self, code: int, where: str, msg: str):
         super().__init__(f"{where}: {_ERRNAMES.get(code, code)}: {msg}")
         self.code = code
@@ -128,6 +134,8 @@ SIGNATURES = {
     "ccrdt_trmv_compact": (INT, [INT, I64, C.POINTER(TrmvOps), C.POINTER(TrmvOps)]),
     "ccrdt_lb_compact": (INT, [I64, C.POINTER(LbOps), C.POINTER(LbOps)]),
     "ccrdt_avg_compact": (INT, [I64, C.POINTER(AvgOps), C.POINTER(AvgOps)]),
+    "ccrdt_trmv_compact_device": (INT, [P, C.POINTER(TrmvOps), C.POINTER(TrmvOps), I64, I64]),
+    "ccrdt_lb_compact_device": (INT, [P, C.POINTER(LbOps), C.POINTER(LbOps), I64]),
     "ccrdt_trmv_apply_device": (INT, [P, C.POINTER(TrmvOps)]),
     "ccrdt_trmv_extra_count": (INT, [P, C.POINTER(I64)]),
     "ccrdt_trmv_fetch_extra": (INT, [P, C.POINTER(TrmvExtra)]),

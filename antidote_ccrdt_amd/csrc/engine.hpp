@@ -113,6 +113,9 @@ struct ccrdt_engine {
   // scan's scratch, the handed-on list (count first), and the host variant's
   // uploaded keys and device-side result
   ccrdt::DevBuf val_cnt, val_caps, val_part, val_list, val_keys, val_ptr, val_id, val_score;
+  // device log compaction (compact_kernels.hip; both types it serves): per-key
+  // kept counts, the scans' scratch, each key's first clock row, the status record
+  ccrdt::DevBuf cmp_cnt, cmp_caps, cmp_part, cmp_rows, cmp_status;
   int trmv_first_tier = 0;
   uint64_t last_n_ops = 0;
   uint64_t trmv_tot[2][3] = {};  // per side: bound on (players, pool, rows) held

@@ -195,6 +195,22 @@ class DeviceArray:
         if self.nbytes:
             check(lib.ccrdt_memcpy_h2d(self.p, ptr(np.ascontiguousarray(host)), self.nbytes), "h2d")
 
+    @classmethod
+    def empty(cls, nbytes: int) -> "DeviceArray":
+        """An uninitialised device buffer of nbytes (an output of a device call)."""
+        d = cls.__new__(cls)
+        d.nbytes, p = int(nbytes), C.c_void_p()
+        check(lib.ccrdt_device_alloc(C.byref(p), max(d.nbytes, 1)), "device_alloc")
+        d.p = p.value
+        return d
+
+    def to_host(self, dtype, n: int | None = None) -> np.ndarray:
+        """The first n elements of dtype (None: the whole buffer) copied to the host."""
+        out = np.empty(self.nbytes // np.dtype(dtype).itemsize if n is None else int(n), dtype)
+        if out.nbytes:
+            check(lib.ccrdt_memcpy_d2h(ptr(out), self.p, out.nbytes), "d2h")
+        return out
+
     def close(self):
         if self.p:
             lib.ccrdt_device_free(self.p)
@@ -209,15 +225,33 @@ class DeviceArray:
 
 class DeviceTrmvBatch:
     """A TrmvBatch resident in HBM (for ccrdt_trmv_apply_device)."""
+    COLUMNS = ("key_ptr", "kind", "id", "score", "dc", "ts", "rmv_vc")
 
     def __init__(self, b: TrmvBatch):
         b = b.normalized()
-        self.n_ops = b.n_ops
-        self.n_rmv = int(b.rmv_vc.shape[0])
-        self.bufs = {f.name: DeviceArray(getattr(b, f.name)) for f in fields(b)}
-        self.c = _lib.TrmvOps(self.n_ops, self.n_rmv, *[self.bufs[n].p for n in
-                                                        ("key_ptr", "kind", "id", "score", "dc",
-                                                         "ts", "rmv_vc")])
+        self._set(b.n_ops, int(b.rmv_vc.shape[0]), {f.name: DeviceArray(getattr(b, f.name)) for f in fields(b)},
+                  int(np.count_nonzero(b.kind >= _lib.TRMV_RMV)))
+
+    def _set(self, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None) -> None:
+        self.n_ops, self.n_rmv, self.bufs = int(n_ops), int(n_rmv), bufs
+        self.n_rmv_ops = n_rmv_ops  # how many ops are rmvs (they may share clock rows); None: not known
+        self.c = _lib.TrmvOps(self.n_ops, self.n_rmv, *[bufs[n].p for n in self.COLUMNS])
+
+    @classmethod
+    def from_buffers(cls, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None = None) -> "DeviceTrmvBatch":
+        """A batch over device buffers that already hold it: bufs maps every
+        name of COLUMNS to a DeviceArray, which the batch owns from here on.
+        n_rmv_ops: how many of its ops are rmvs, where the producer knows."""
+        db = cls.__new__(cls)
+        db._set(n_ops, n_rmv, bufs, n_rmv_ops)
+        return db
+
+    def to_host(self, n_dc: int) -> TrmvBatch:
+        """The batch copied back to the host (n_ops ops, n_rmv clock rows of n_dc)."""
+        n, r, b = self.n_ops, self.n_rmv, self.bufs
+        return TrmvBatch(b["key_ptr"].to_host(np.uint64), b["kind"].to_host(np.uint8, n), b["id"].to_host(np.int64, n),
+                         b["score"].to_host(np.int64, n), b["dc"].to_host(np.uint8, n), b["ts"].to_host(np.int64, n),
+                         b["rmv_vc"].to_host(np.int64, r * n_dc).reshape(r, n_dc))
 
     def close(self):
         for d in self.bufs.values():
@@ -358,6 +392,36 @@ class TopkRmvEngine(_Engine):
 
     def apply_device(self, db: DeviceTrmvBatch) -> None:
         self._checked(lib.ccrdt_trmv_apply_device(self.h, C.byref(db.c)), "trmv_apply_device")
+
+    def compact_device(self, db: DeviceTrmvBatch, cap_ops: int | None = None,
+                       cap_rows: int | None = None) -> DeviceTrmvBatch:
+        """Log compaction of a batch resident in HBM (ccrdt_trmv_compact_device):
+        compact_trmv's result, bit for bit, as a new device batch that
+        apply_device takes as it is.  The outputs hold cap_ops ops and cap_rows
+        clock rows.  cap_ops defaults to the input's op count.  Every output
+        rmv owns one row (an input whose rmvs share rows can need more rows
+        than it has), so cap_rows defaults to the input's count of rmv ops
+        (db.n_rmv_ops), which always suffices; a batch that does not know it
+        gets room for n_ops rows, 8 * n_dc bytes each: pass cap_rows for a
+        large one.  A compacted batch over either capacity raises
+        CcrdtError(ENOMEM) whose `totals` = (ops, clock rows) say what to call
+        again with."""
+        cap_ops = db.n_ops if cap_ops is None else int(cap_ops)
+        if cap_rows is None:
+            cap_rows = db.n_ops if db.n_rmv_ops is None else db.n_rmv_ops
+        size = {"key_ptr": 8 * (self.n_keys + 1), "kind": cap_ops, "id": 8 * cap_ops, "score": 8 * cap_ops,
+                "dc": cap_ops, "ts": 8 * cap_ops, "rmv_vc": 8 * cap_rows * self.n_dc}
+        bufs = {n: DeviceArray.empty(size[n]) for n in DeviceTrmvBatch.COLUMNS}
+        co = _lib.TrmvOps(0, 0, *[bufs[n].p for n in DeviceTrmvBatch.COLUMNS])
+        try:
+            check(lib.ccrdt_trmv_compact_device(self.h, C.byref(db.c), C.byref(co), cap_ops, cap_rows),
+                  "trmv_compact_device")
+        except _lib.CcrdtError as err:
+            err.totals = (int(co.n_ops), int(co.n_rmv_rows))
+            for d in bufs.values():
+                d.close()
+            raise
+        return DeviceTrmvBatch.from_buffers(co.n_ops, co.n_rmv_rows, bufs, n_rmv_ops=co.n_rmv_rows)
 
     def _checked(self, rc: int, where: str, extra=None) -> None:
         """check(), with the keys left out attached to KeyCapacityError

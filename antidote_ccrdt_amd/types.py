@@ -179,6 +179,23 @@ class LeaderboardEngine(_Engine):
         ops = _lib.LbOps(d.n, d["key_ptr"], d["kind"], d["id"], d["score"])
         check(lib.ccrdt_lb_apply_device(self.h, C.byref(ops)), "lb_apply_device")
 
+    def compact_device(self, d: "DeviceBatch") -> "DeviceBatch":
+        """Log compaction of a batch resident in HBM (ccrdt_lb_compact_device):
+        compact_lb's result, bit for bit, as a new device batch (n = the
+        compacted op count) that apply_device takes as it is."""
+        from .engine import DeviceArray
+        size = {"key_ptr": 8 * (self.n_keys + 1), "kind": d.n, "id": 8 * d.n, "score": 8 * d.n}
+        out = DeviceBatch.from_buffers(0, {k: DeviceArray.empty(v) for k, v in size.items()})
+        co = _lib.LbOps(0, out["key_ptr"], out["kind"], out["id"], out["score"])
+        ci = _lib.LbOps(d.n, d["key_ptr"], d["kind"], d["id"], d["score"])
+        try:
+            check(lib.ccrdt_lb_compact_device(self.h, C.byref(ci), C.byref(co), d.n), "lb_compact_device")
+        except _lib.CcrdtError:
+            out.close()
+            raise
+        out.n = int(co.n_ops)
+        return out
+
     def values(self, keys=None):
         """value/1 (leaderboard.erl:84-86) of `keys` (board indices in any
         order, repeats allowed; None: every board) read on the device: (ptr,
@@ -387,6 +404,13 @@ class DeviceBatch:
         from .engine import DeviceArray
         self.n = n
         self.bufs = {k: DeviceArray(np.ascontiguousarray(v)) for k, v in arrays.items()}
+
+    @classmethod
+    def from_buffers(cls, n: int, bufs: dict) -> "DeviceBatch":
+        """A batch over DeviceArrays that already hold it; the batch owns them."""
+        d = cls.__new__(cls)
+        d.n, d.bufs = n, bufs
+        return d
 
     def __getitem__(self, k):
         return self.bufs[k].p

@@ -198,7 +198,9 @@ typedef struct {
  * halves are dropped).  `out` arrays have the input's capacity (n_ops ops,
  * n_ops * n_dc clock values); out->key_ptr has n_keys + 1 entries.  Every
  * output rmv gets its own clock row (merged Vcs included), numbered in
- * stream order; out->n_ops / out->n_rmv_rows are set.  Host only. */
+ * stream order; out->n_ops / out->n_rmv_rows are set.  Host only.  A batch
+ * that already lies in HBM is compacted there by ccrdt_trmv_compact_device
+ * (leaderboard: ccrdt_lb_compact_device). */
 typedef struct {
   int64_t n_ops;
   int64_t n_rmv_rows;
@@ -211,6 +213,29 @@ typedef struct {
   int64_t* rmv_vc;
 } ccrdt_trmv_batch;
 int ccrdt_trmv_compact(int n_dc, int64_t n_keys, const ccrdt_trmv_ops* in, ccrdt_trmv_batch* out);
+/* ccrdt_trmv_compact over a batch resident in HBM; the result is bit-identical
+ * to ccrdt_trmv_compact on the same arrays (same CSR, every output rmv its own
+ * clock row numbered in stream order with ts = that row, score = dc = 0 on
+ * rmvs), so it can be handed to ccrdt_trmv_apply_device as it is.  n_keys and
+ * n_dc are the engine's; dev_in->n_ops / ->n_rmv_rows are host values; every
+ * array pointer of dev_in and dev_out is device memory and dev_out must not
+ * overlap dev_in.  dev_out's op arrays hold cap_ops ops, its rmv_vc
+ * cap_rows * n_dc values, its key_ptr n_keys + 1 entries.  The work is
+ * enqueued on the engine stream; the call then reads back one small status
+ * record (output op total, output clock-row total, error word), its only wait,
+ * and sets dev_out->n_ops / ->n_rmv_rows from it.  The engine's resident state
+ * is neither read nor changed (a fresh, a reset and a populated engine serve
+ * alike).  dev_out->key_ptr[0 .. n_keys] is always written in full.
+ * CCRDT_ENOMEM: the op total exceeds cap_ops or the row total cap_rows; the
+ * true totals are still set (size the outputs by them and call again) and
+ * nothing at or past either capacity is written.  CCRDT_EINVAL, as for the
+ * host compactor: a kind above 3, a rmv clock row outside [0, n_rmv_rows), an
+ * add's dc >= n_dc, key_ptr[n_keys] != n_ops (or a key's ops outside
+ * [0, n_ops), or 2^32 ops or more in one key), null arrays with n_ops > 0, an
+ * engine of another type; an invalid batch writes no ops or rows.  After any
+ * error the engine stays usable.  n_ops == 0 is valid: all of key_ptr is 0. */
+int ccrdt_trmv_compact_device(ccrdt_engine* e, const ccrdt_trmv_ops* dev_in, ccrdt_trmv_batch* dev_out,
+                              int64_t cap_ops, int64_t cap_rows);
 
 /* Extra effects ({ok, State, [Effect]}, at most one per op — SURVEY Q3),
  * indexed by op.  kind[i] = CCRDT_NOOP when op i returned {ok, State}.
@@ -466,6 +491,11 @@ typedef struct {
   int64_t* score;
 } ccrdt_lb_batch;
 int ccrdt_lb_compact(int64_t n_keys, const ccrdt_lb_ops* in, ccrdt_lb_batch* out);
+/* ccrdt_lb_compact over a batch resident in HBM, bit-identical to it (score =
+ * 0 on bans); arguments, the status read-back, capacities and errors as
+ * ccrdt_trmv_compact_device (a kind above 2 is CCRDT_EINVAL; no clock rows).
+ * The result can be handed to ccrdt_lb_apply_device as it is. */
+int ccrdt_lb_compact_device(ccrdt_engine* e, const ccrdt_lb_ops* dev_in, ccrdt_lb_batch* dev_out, int64_t cap_ops);
 /* Extra effects, op-indexed: kind CCRDT_LB_ADD = {add, {Id, Score}} from a
  * ban that promoted a Masked player (:279-283), CCRDT_NOOP = none. */
 typedef struct {
