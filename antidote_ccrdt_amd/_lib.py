@@ -21,6 +21,9 @@ AVERAGE, TOPK, TOPK_RMV, LEADERBOARD, WORDCOUNT, WORDDOCUMENTCOUNT = range(6)
 TRMV_ADD, TRMV_ADD_R, TRMV_RMV, TRMV_RMV_R = range(4)
 NOOP = 255
 TRMV_MAX_DC = 8
+# the run merge (ccrdt_trmv_merge_runs_device): runs per call, ops of one run per workgroup of its rank pass
+TRMV_MAX_RUNS = 32
+TRMV_MERGE_TILE = 256
 
 P = C.c_void_p
 I64 = C.c_int64
@@ -30,7 +33,7 @@ INT = C.c_int
 
 class CcrdtError(RuntimeError):
     """A CCRDT_* return code other than OK (`code`).  Raised by
-    TopkRmvEngine.compact_device, it carries `totals` = (ops, clock rows) of
+    TopkRmvEngine.compact_device, merge_runs_device or extras_run_device, it carries `totals` = (ops, clock rows) of
     the compacted batch as far as the call got to set them: with ENOMEM the
     true totals, to size the outputs by."""
     totals = None
@@ -64,6 +67,11 @@ _ERRNAMES = {EINVAL: "EINVAL", ERANGE: "ERANGE", ENOMEM: "ENOMEM", EDEVICE: "EDE
 
 class TrmvOps(C.Structure):
     _fields_ = [("n_ops", I64), ("n_rmv_rows", I64), ("key_ptr", P), ("kind", P), ("id", P),
+                ("score", P), ("dc", P), ("ts", P), ("rmv_vc", P)]
+
+
+class TrmvRun(C.Structure):
+    _fields_ = [("n_ops", I64), ("n_rmv_rows", I64), ("key", P), ("kind", P), ("id", P),
                 ("score", P), ("dc", P), ("ts", P), ("rmv_vc", P)]
 
 
@@ -136,6 +144,8 @@ SIGNATURES = {
     "ccrdt_avg_compact": (INT, [I64, C.POINTER(AvgOps), C.POINTER(AvgOps)]),
     "ccrdt_trmv_compact_device": (INT, [P, C.POINTER(TrmvOps), C.POINTER(TrmvOps), I64, I64]),
     "ccrdt_lb_compact_device": (INT, [P, C.POINTER(LbOps), C.POINTER(LbOps), I64]),
+    "ccrdt_trmv_merge_runs_device": (INT, [P, INT, C.POINTER(TrmvRun), C.POINTER(TrmvOps), I64, I64]),
+    "ccrdt_trmv_extras_run_device": (INT, [P, C.POINTER(TrmvOps), P, I64, I64]),
     "ccrdt_trmv_apply_device": (INT, [P, C.POINTER(TrmvOps)]),
     "ccrdt_trmv_extra_count": (INT, [P, C.POINTER(I64)]),
     "ccrdt_trmv_fetch_extra": (INT, [P, C.POINTER(TrmvExtra)]),

@@ -1201,3 +1201,213 @@ def lb_replicate_device_local(engines, batches, max_rounds: int = 64) -> int:
             return rounds
         outs = [r.deliver(outs) for r in reps]
     raise RuntimeError("replication did not quiesce")
+
+
+# ------------------------- topk_rmv replication mode, on the device
+# The protocol of ReplicatedTopkRmv with every effect kept in HBM.  A replica's
+# message for one delivery round is one flat int64 tensor of RUNS
+# (ccrdt_trmv_run: effects of one origin in seq order, sorted by key): its
+# first message is its batch and then the batch's extras, later messages one
+# run of extras.  Layout: a header of _TRMV_HDR words
+# [n_runs | failed << 32, then per run: ops, clock rows, rmv ops], then per run
+# the columns key, kind, id, score, dc, ts (n words each) and its clock rows
+# (rows x n_dc words); an empty message is a zero-length tensor.  The canonical
+# (key, origin, seq) order of the host protocol is the merge of the gathered
+# runs taken in (origin, message position) order, done by
+# ccrdt_trmv_merge_runs_device; the extras come back as a run in stream order
+# from ccrdt_trmv_extras_run_device.  torch only packs and unpacks columns.
+_TRMV_HDR = 8
+_TRMV_FAIL = 1 << 32
+
+
+class _TensorBuf:
+    """A torch tensor as a device buffer of the engine API (`.p`, `.close()`)."""
+
+    def __init__(self, t):
+        self.t, self.p, self.nbytes = t, t.data_ptr(), t.numel() * t.element_size()
+
+    def to_host(self, dtype, n=None):
+        a = self.t.cpu().numpy().reshape(-1).view(np.uint8).view(dtype)
+        return a if n is None else a[:int(n)]
+
+    def close(self):
+        self.t = self.p = None
+
+
+def _dev_tensor(buf, dtype, n: int, device):
+    """The first n elements of a device buffer (a _TensorBuf, or a DeviceArray
+    through its device pointer) as a torch tensor of dtype, without a copy."""
+    import torch
+    if not n:
+        return torch.empty(0, dtype=dtype, device=device)
+    if isinstance(buf, _TensorBuf):
+        return buf.t.reshape(-1).view(torch.uint8).view(dtype)[:n]
+
+    class _Cai:
+        __cuda_array_interface__ = {"shape": (int(n),), "typestr": "|u1" if dtype == torch.uint8 else "<i8",
+                                    "data": (buf.p, False), "version": 2}
+    return torch.as_tensor(_Cai(), device=device)
+
+
+def _trmv_message(runs, n_dc: int, device, failed: bool = False):
+    """The message of DeviceTrmvRuns (None and empty ones left out)."""
+    import torch
+
+    from .engine import DeviceTrmvRun
+    runs = [r for r in runs if r is not None and r.n_ops]
+    if not runs and not failed:
+        return torch.empty(0, dtype=torch.int64, device=device)
+    hdr = [len(runs) | (_TRMV_FAIL if failed else 0)]
+    parts = []
+    for r in runs:
+        hdr += [r.n_ops, r.n_rmv, r.n_ops if r.n_rmv_ops is None else r.n_rmv_ops]
+        for c, dt in zip(DeviceTrmvRun.COLUMNS[:-1], DeviceTrmvRun.DTYPES):
+            parts.append(_dev_tensor(r.bufs[c], torch.uint8 if dt == np.uint8 else torch.int64, r.n_ops,
+                                     device).to(torch.int64))
+        parts.append(_dev_tensor(r.bufs["rmv_vc"], torch.int64, r.n_rmv * n_dc, device))
+    hdr += [0] * (_TRMV_HDR - len(hdr))
+    return torch.cat([torch.tensor(hdr, dtype=torch.int64, device=device)] + parts)
+
+
+def _trmv_headers(msgs):
+    """Each message's header as a list of ints (None for an empty message): one host read."""
+    import torch
+    full = [m for m in msgs if int(m.shape[0])]
+    hv = iter(torch.stack([m[:_TRMV_HDR] for m in full]).cpu().tolist() if full else [])
+    return [next(hv) if int(m.shape[0]) else None for m in msgs]
+
+
+def _trmv_unpack(msg, hdr, n_dc: int):
+    """The runs of one message, as DeviceTrmvRuns over slices of it."""
+    import torch
+
+    from .engine import DeviceTrmvRun
+    off, runs = _TRMV_HDR, []
+    for j in range(hdr[0] & 0xFFFFFFFF):
+        n, rows, n_rmv_ops = hdr[1 + 3 * j:4 + 3 * j]
+        cols = {}
+        for c, dt in zip(DeviceTrmvRun.COLUMNS[:-1], DeviceTrmvRun.DTYPES):
+            t = msg[off:off + n]
+            cols[c] = _TensorBuf(t.to(torch.uint8) if dt == np.uint8 else t)
+            off += n
+        cols["rmv_vc"] = _TensorBuf(msg[off:off + rows * n_dc])
+        off += rows * n_dc
+        runs.append(DeviceTrmvRun.from_buffers(n, rows, cols, n_rmv_ops))
+    return runs
+
+
+class TrmvDeviceReplica:
+    """One DC replica of an n_keys topk_rmv keyspace with its effects on the
+    device (BASELINE configs[3]): the protocol of ReplicatedTopkRmv
+    (topk_rmv.erl:140-148; extras :236-237, :294-295), whose canonical (key,
+    origin, seq) order the run merge reproduces.  A step is originate() and
+    then deliver() per round, each returning the message (above) this replica
+    sends; the exchange between them is injected: trmv_replicate_step with a
+    TorchCollective (one process per GPU) or trmv_replicate_device_local
+    (replicas held by one process).  Both run exactly these two methods.
+    The host reads of a delivery are the gathered headers, the status records
+    of the merge and of the extras run, and apply_device's own.  A key over
+    the engine's per-key capacity makes apply_device raise KeyCapacityError
+    (the batch committed for every other key); the drivers say what happens
+    then.  Continuing such keys on the host path stays with ReplicatedTopkRmv."""
+
+    def __init__(self, engine, rank: int, world: int):
+        import torch
+        self.engine, self.rank, self.world = engine, rank, world
+        self.dev = torch.device("cuda", engine.device)
+
+    def _alloc(self, nbytes: int):
+        import torch
+        return _TensorBuf(torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.dev))
+
+    def _apply(self, db):
+        """apply_device(db) after torch's queued work; the extras as a run (at
+        most one per op, a rmv only from an add)."""
+        import torch
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.dev))
+        self.engine.apply_device(db)
+        return self.engine.extras_run_device(db.n_ops, db.n_ops - (db.n_rmv_ops or 0), alloc=self._alloc)
+
+    def originate(self, batch):
+        """Apply this replica's own DeviceTrmvBatch (CSR by key, stream order:
+        already canonical for one origin) and return its message: the batch as
+        a run, its key column expanded from key_ptr, and then its extras."""
+        import torch
+
+        from .engine import DeviceTrmvRun
+        ex = self._apply(batch)
+        n, nk = batch.n_ops, self.engine.n_keys
+        kp = _dev_tensor(batch.bufs["key_ptr"], torch.int64, nk + 1, self.dev)
+        key = torch.repeat_interleave(torch.arange(nk, device=self.dev), kp[1:] - kp[:-1], output_size=n)
+        own = DeviceTrmvRun.from_buffers(n, batch.n_rmv, {"key": _TensorBuf(key), **{
+            c: batch.bufs[c] for c in DeviceTrmvRun.COLUMNS[1:]}}, batch.n_rmv_ops)
+        return _trmv_message([own, ex], self.engine.n_dc, self.dev)
+
+    def deliver(self, parts, hdrs=None):
+        """Apply the messages of every other origin (parts[o] = origin o's;
+        hdrs = _trmv_headers(parts) where the caller has read them) merged
+        into canonical order; returns the message of the extras that produced."""
+        import torch
+        hdrs = _trmv_headers(parts) if hdrs is None else hdrs
+        runs = [r for o, (p, h) in enumerate(zip(parts, hdrs)) if o != self.rank and h is not None
+                for r in _trmv_unpack(p.to(self.dev), h, self.engine.n_dc)]
+        if not runs:
+            return _trmv_message([], self.engine.n_dc, self.dev)
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.dev))
+        merged = self.engine.merge_runs_device(runs, alloc=self._alloc)
+        return _trmv_message([self._apply(merged)], self.engine.n_dc, self.dev)
+
+
+def trmv_replicate_step(replica: TrmvDeviceReplica, batch, coll, max_rounds: int = 64) -> int:
+    """One replication step of this rank's replica over a collective
+    (TorchCollective: RCCL over xGMI, or gloo staged through the host);
+    returns the number of delivery rounds.  A rank whose apply raises (a key
+    over the per-key capacity, an invalid op, a device error) sends a message
+    whose header carries the failure word, still takes part in the gather, and
+    then every rank raises PeerStepError (the failed rank's own exception
+    chained), so no rank is left in a collective."""
+    def guarded(fn, *args):
+        try:
+            return fn(*args), None
+        except Exception as e:  # noqa: BLE001 - re-raised on every rank after the gather
+            return _trmv_message([], replica.engine.n_dc, replica.dev, failed=True), e
+    out, err = guarded(replica.originate, batch)
+    for rounds in range(max_rounds):
+        parts = coll.all_gather_v(out)
+        hdrs = _trmv_headers(parts)
+        failed = [r for r, h in enumerate(hdrs) if h is not None and h[0] & _TRMV_FAIL]
+        if failed:
+            raise PeerStepError(failed) from err
+        if all(h is None for h in hdrs):
+            return rounds
+        out, err = guarded(replica.deliver, parts, hdrs)
+    raise RuntimeError("replication did not quiesce")
+
+
+def trmv_replicate_device_local(engines, batches, max_rounds: int = 64) -> int:
+    """trmv_replicate_step for several replicas held by one process (the
+    all-gather is the list of every replica's messages).  `batches` are
+    DeviceTrmvBatches, CSR by key.  Returns the number of delivery rounds.  A
+    KeyCapacityError of a replica's apply_device propagates once every replica
+    has applied the round."""
+    from ._lib import KeyCapacityError
+    reps = [TrmvDeviceReplica(e, r, len(engines)) for r, e in enumerate(engines)]
+
+    def round_of(calls):
+        outs, first = [], None
+        for r, (fn, args) in zip(reps, calls):
+            try:
+                outs.append(fn(*args))
+            except KeyCapacityError as e:
+                first = first or e
+                outs.append(_trmv_message([], r.engine.n_dc, r.dev))
+        if first is not None:
+            raise first
+        return outs
+    outs = round_of([(r.originate, (b,)) for r, b in zip(reps, batches)])
+    for rounds in range(max_rounds):
+        hdrs = _trmv_headers(outs)
+        if all(h is None for h in hdrs):
+            return rounds
+        outs = round_of([(r.deliver, (outs, hdrs)) for r in reps])
+    raise RuntimeError("replication did not quiesce")

@@ -94,7 +94,7 @@ void ccrdt_engine::release_all() {
   for (DevBuf* d : {&arena, &obs_ord, &key_done, &partials, &ex_cnt, &ex, &ex_vc, &ex_key_ptr, &status, &op_pl,
                     &first_list, &ovl,
                     &hbm_scratch, &val_cnt, &val_caps, &val_part, &val_list, &val_keys, &val_ptr, &val_id,
-                    &val_score, &cmp_cnt, &cmp_caps, &cmp_part, &cmp_rows, &cmp_status, &st_kp,
+                    &val_score, &cmp_cnt, &cmp_caps, &cmp_part, &cmp_rows, &cmp_status, &rpl_src, &rpl_key, &rpl_off, &st_kp,
                     &st_kind, &st_id, &st_score, &st_dc, &st_ts, &st_rvc, &st_out_kind, &st_out_vc})
     d->release();
   wcv.release();

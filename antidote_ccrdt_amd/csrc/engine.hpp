@@ -116,6 +116,10 @@ struct ccrdt_engine {
   // device log compaction (compact_kernels.hip; both types it serves): per-key
   // kept counts, the scans' scratch, each key's first clock row, the status record
   ccrdt::DevBuf cmp_cnt, cmp_caps, cmp_part, cmp_rows, cmp_status;
+  // replication mode (replicate_kernels.hip; it shares the compaction's scan
+  // scratch and status record): by output position the op's source and key;
+  // the extras run's per-key output offsets
+  ccrdt::DevBuf rpl_src, rpl_key, rpl_off;
   int trmv_first_tier = 0;
   uint64_t last_n_ops = 0;
   uint64_t trmv_tot[2][3] = {};  // per side: bound on (players, pool, rows) held

@@ -258,6 +258,60 @@ class DeviceTrmvBatch:
             d.close()
 
 
+@dataclass
+class TrmvRun:
+    """A run of topk_rmv effects on the host (layout of ccrdt_trmv_run): effects
+    of one origin in its sequence order, sorted by key; key[i] is op i's key."""
+    key: np.ndarray     # int64 [n_ops], non-decreasing
+    kind: np.ndarray
+    id: np.ndarray
+    score: np.ndarray
+    dc: np.ndarray
+    ts: np.ndarray      # rmv: row of rmv_vc
+    rmv_vc: np.ndarray  # int64 [n_rmv, n_dc]
+
+    @classmethod
+    def of_batch(cls, b: TrmvBatch) -> "TrmvRun":
+        """A CSR batch as a run: the key column expanded from key_ptr."""
+        b = b.normalized()
+        key = np.repeat(np.arange(b.n_keys, dtype=np.int64), np.diff(b.key_ptr.astype(np.int64)))
+        return cls(key, b.kind, b.id, b.score, b.dc, b.ts, b.rmv_vc)
+
+
+class DeviceTrmvRun:
+    """A TrmvRun resident in HBM (for ccrdt_trmv_merge_runs_device)."""
+    COLUMNS = ("key", "kind", "id", "score", "dc", "ts", "rmv_vc")
+    DTYPES = (np.int64, np.uint8, np.int64, np.int64, np.uint8, np.int64, np.int64)
+
+    def __init__(self, r: TrmvRun):
+        cols = {n: DeviceArray(_c(getattr(r, n), dt)) for n, dt in zip(self.COLUMNS, self.DTYPES)}
+        self._set(int(r.kind.shape[0]), int(r.rmv_vc.shape[0]), cols, int(np.count_nonzero(r.kind >= _lib.TRMV_RMV)))
+
+    def _set(self, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None) -> None:
+        self.n_ops, self.n_rmv, self.bufs = int(n_ops), int(n_rmv), bufs
+        self.n_rmv_ops = n_rmv_ops  # how many ops are rmvs (they may share clock rows); None: not known
+        self.c = _lib.TrmvRun(self.n_ops, self.n_rmv, *[bufs[n].p for n in self.COLUMNS])
+
+    @classmethod
+    def from_buffers(cls, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None = None) -> "DeviceTrmvRun":
+        """A run over device buffers that already hold it: bufs maps every name
+        of COLUMNS to a buffer with a device pointer `.p` (a DeviceArray), which
+        the run owns from here on."""
+        dr = cls.__new__(cls)
+        dr._set(n_ops, n_rmv, bufs, n_rmv_ops)
+        return dr
+
+    def to_host(self, n_dc: int) -> TrmvRun:
+        """The run copied back to the host (n_ops ops, n_rmv clock rows of n_dc)."""
+        n, r = self.n_ops, self.n_rmv
+        cols = [self.bufs[c].to_host(dt, n) for c, dt in zip(self.COLUMNS[:-1], self.DTYPES)]
+        return TrmvRun(*cols, self.bufs["rmv_vc"].to_host(np.int64, r * n_dc).reshape(r, n_dc))
+
+    def close(self):
+        for d in self.bufs.values():
+            d.close()
+
+
 class _Engine:
     TYPE = -1
 
@@ -422,6 +476,67 @@ class TopkRmvEngine(_Engine):
                 d.close()
             raise
         return DeviceTrmvBatch.from_buffers(co.n_ops, co.n_rmv_rows, bufs, n_rmv_ops=co.n_rmv_rows)
+
+    def _op_bufs(self, names, cap_ops: int, cap_rows: int, alloc) -> dict:
+        """Uninitialised output buffers of a device call: cap_ops ops, cap_rows clock rows."""
+        size = {"key_ptr": 8 * (self.n_keys + 1), "key": 8 * cap_ops, "kind": cap_ops, "id": 8 * cap_ops,
+                "score": 8 * cap_ops, "dc": cap_ops, "ts": 8 * cap_ops, "rmv_vc": 8 * cap_rows * self.n_dc}
+        return {n: alloc(size[n]) for n in names}
+
+    def _sized_call(self, fn, where: str, co, bufs: dict, *args) -> None:
+        """A device call that sets co.n_ops / co.n_rmv_rows: an error frees the
+        outputs and carries the totals (with ENOMEM the true ones)."""
+        try:
+            check(fn(self.h, *args), where)
+        except _lib.CcrdtError as err:
+            err.totals = (int(co.n_ops), int(co.n_rmv_rows))
+            for d in bufs.values():
+                d.close()
+            raise
+
+    def merge_runs_device(self, runs, cap_ops: int | None = None, cap_rows: int | None = None,
+                          alloc=DeviceArray.empty) -> DeviceTrmvBatch:
+        """1 .. TRMV_MAX_RUNS DeviceTrmvRuns, given in (origin, sequence) order,
+        merged on the device into the one batch of the canonical order (key,
+        origin, seq) (ccrdt_trmv_merge_runs_device), which apply_device and
+        compact_device take as it is: every rmv owns one clock row, numbered in
+        stream order.  cap_ops defaults to the runs' op total, cap_rows to
+        their rmv total (a run that does not know its rmv count gets room for
+        a row per op).  A result over either capacity raises
+        CcrdtError(ENOMEM) whose `totals` = (ops, clock rows).  `alloc`
+        (bytes -> a buffer with `.p` and `.close()`) provides the outputs."""
+        runs = list(runs)
+        if cap_ops is None:
+            cap_ops = sum(r.n_ops for r in runs)
+        if cap_rows is None:
+            cap_rows = sum(r.n_ops if r.n_rmv_ops is None else r.n_rmv_ops for r in runs)
+        bufs = self._op_bufs(DeviceTrmvBatch.COLUMNS, int(cap_ops), int(cap_rows), alloc)
+        co = _lib.TrmvOps(0, 0, *[bufs[n].p for n in DeviceTrmvBatch.COLUMNS])
+        cr = (_lib.TrmvRun * max(len(runs), 1))(*[r.c for r in runs])
+        self._sized_call(lib.ccrdt_trmv_merge_runs_device, "trmv_merge_runs_device", co, bufs, len(runs), cr,
+                         C.byref(co), int(cap_ops), int(cap_rows))
+        return DeviceTrmvBatch.from_buffers(co.n_ops, co.n_rmv_rows, bufs, n_rmv_ops=co.n_rmv_rows)
+
+    def extras_run_device(self, cap_ops: int | None = None, cap_rows: int | None = None,
+                          alloc=DeviceArray.empty) -> DeviceTrmvRun | None:
+        """The last apply's extra effects as a run in (key, op index) order, on
+        the device (ccrdt_trmv_extras_run_device): the stream order the host
+        protocol re-broadcasts them in; None when there are none.  Both
+        capacities default to extra_count() (a host read of the per-key
+        counts: a caller that knows a bound passes it); over either raises
+        CcrdtError(ENOMEM) with `totals`."""
+        if cap_ops is None or cap_rows is None:
+            n = self.extra_count()
+            cap_ops, cap_rows = (n if cap_ops is None else cap_ops), (n if cap_rows is None else cap_rows)
+        bufs = self._op_bufs(DeviceTrmvRun.COLUMNS, int(cap_ops), int(cap_rows), alloc)
+        co = _lib.TrmvOps(0, 0, None, *[bufs[n].p for n in DeviceTrmvRun.COLUMNS[1:]])
+        self._sized_call(lib.ccrdt_trmv_extras_run_device, "trmv_extras_run_device", co, bufs, C.byref(co),
+                         bufs["key"].p, int(cap_ops), int(cap_rows))
+        if not co.n_ops:
+            for d in bufs.values():
+                d.close()
+            return None
+        return DeviceTrmvRun.from_buffers(co.n_ops, co.n_rmv_rows, bufs, n_rmv_ops=co.n_rmv_rows)
 
     def _checked(self, rc: int, where: str, extra=None) -> None:
         """check(), with the keys left out attached to KeyCapacityError

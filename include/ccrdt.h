@@ -237,6 +237,67 @@ int ccrdt_trmv_compact(int n_dc, int64_t n_keys, const ccrdt_trmv_ops* in, ccrdt
 int ccrdt_trmv_compact_device(ccrdt_engine* e, const ccrdt_trmv_ops* dev_in, ccrdt_trmv_batch* dev_out,
                               int64_t cap_ops, int64_t cap_rows);
 
+/* A run of topk_rmv effects: what one replica contributes to a delivery of the
+ * replication mode -- effects of one origin in that origin's sequence order,
+ * sorted by key (non-decreasing).  COO: key[i] is op i's key; every other field
+ * is as in ccrdt_trmv_ops (a rmv's ts is its row of the run's own rmv_vc; rows
+ * may be shared between the rmvs of a run). */
+typedef struct {
+  int64_t n_ops;
+  int64_t n_rmv_rows;
+  const int64_t* key;    /* [n_ops] non-decreasing, in [0, n_keys) */
+  const uint8_t* kind;   /* [n_ops] */
+  const int64_t* id;     /* [n_ops] */
+  const int64_t* score;  /* [n_ops] */
+  const uint8_t* dc;     /* [n_ops] */
+  const int64_t* ts;     /* [n_ops] */
+  const int64_t* rmv_vc; /* [n_rmv_rows * n_dc] */
+} ccrdt_trmv_run;
+/* Runs per merge; ops of one run a workgroup of the merge's rank pass takes. */
+#define CCRDT_TRMV_MAX_RUNS 32
+#define CCRDT_TRMV_MERGE_TILE 256
+/* n_runs runs, given in (origin, sequence) order, merged on the device into
+ * the one CSR batch of the canonical order (key, origin, seq): per key run 0's
+ * ops of that key, then run 1's, and so on, each run's own order kept (what
+ * the host protocol gets by sorting the gathered rows, cluster.canonical, and
+ * rebuilding the CSR).  dev_runs is a host array of n_runs structs whose
+ * n_ops / n_rmv_rows are host values and whose array pointers are device
+ * memory; dev_out is laid out as for ccrdt_trmv_compact_device (cap_ops ops,
+ * cap_rows * n_dc clock values, key_ptr n_keys + 1 entries) and must not
+ * overlap a run.  n_keys and n_dc are the engine's.  Adds keep dc and ts;
+ * every output rmv owns one clock row numbered in output stream order with ts
+ * = that row and score = dc = 0, so the result can be handed to
+ * ccrdt_trmv_apply_device (or ccrdt_trmv_compact_device) as it is.  The work
+ * is enqueued on the engine stream; the call then reads back one small status
+ * record (op total, clock-row total, error word), its only wait, and sets
+ * dev_out->n_ops / ->n_rmv_rows from it.  The engine's resident state is
+ * neither read nor changed.  CCRDT_ENOMEM: the op total exceeds cap_ops or the
+ * rmv total cap_rows; the true totals are still set, key_ptr[0 .. n_keys] is
+ * written in full and nothing at or past either capacity is written.
+ * CCRDT_EINVAL, with nothing written to dev_out's arrays: a run whose keys
+ * decrease, a key outside [0, n_keys), a kind above 3, an add's dc >= n_dc, a
+ * rmv clock row outside [0, n_rmv_rows) of its run, null arrays with n_ops >
+ * 0, 2^32 ops or more in all, n_runs outside [1, CCRDT_TRMV_MAX_RUNS], an
+ * engine of another type.  After any error the engine stays usable.  No ops in
+ * any run is valid: all of key_ptr is 0. */
+int ccrdt_trmv_merge_runs_device(ccrdt_engine* e, int n_runs, const ccrdt_trmv_run* dev_runs,
+                                 ccrdt_trmv_batch* dev_out, int64_t cap_ops, int64_t cap_rows);
+/* The extra effects of the last ccrdt_trmv_apply / _apply_device as a run, in
+ * (key, op index) order -- the stream order the host protocol re-broadcasts
+ * them in.  d_key[i] (device, cap_ops entries) is effect i's key; the columns
+ * of dev_out_cols (device; key_ptr unused, may be NULL) hold kind
+ * (CCRDT_TRMV_ADD = promotion {add, {Id, Score, {Dc, Ts}}}, topk_rmv.erl:295;
+ * CCRDT_TRMV_RMV = {rmv, {Id, Vc}}, :237), id, and for adds score, dc, ts;
+ * every rmv owns one clock row numbered in output order with ts = that row and
+ * score = dc = 0.  Enqueued on the engine stream after the apply; the status
+ * read-back, dev_out_cols->n_ops / ->n_rmv_rows, CCRDT_ENOMEM with the true
+ * totals and nothing written at or past a capacity are as for
+ * ccrdt_trmv_merge_runs_device.  No extras (or no apply yet) is valid: n_ops =
+ * 0.  The resident state and the extras themselves are not changed
+ * (ccrdt_trmv_fetch_extra / _extras_device still serve them). */
+int ccrdt_trmv_extras_run_device(ccrdt_engine* e, ccrdt_trmv_batch* dev_out_cols, int64_t* d_key, int64_t cap_ops,
+                                 int64_t cap_rows);
+
 /* Extra effects ({ok, State, [Effect]}, at most one per op — SURVEY Q3),
  * indexed by op.  kind[i] = CCRDT_NOOP when op i returned {ok, State}.
  *   CCRDT_TRMV_ADD -> {add, {Id, Score, {Dc, Ts}}}   promotion (topk_rmv.erl:295)
