@@ -259,6 +259,36 @@ __device__ __forceinline__ uint32_t wave_excl_scan_dpp(uint32_t v, uint32_t& tot
   total = rl32(inc, 63);
   return inc - v;
 }
+// Bitonic sort of m elements by one workgroup of BLOCK threads (every thread
+// calls it), every compare-exchange in the same direction: a stage's first
+// step mirrors the second half of each block instead of alternating
+// directions.  cmpx(lo, hi), lo < hi < m, is the caller's compare-exchange of
+// two positions.  Positions >= m stand for elements that rank last: an
+// exchange with one of them never moves anything, so it is skipped, the
+// padding is never loaded or stored, and no sentinel value is needed.  Ends
+// in __syncthreads.
+template <int BLOCK, class CmpX>
+__device__ __forceinline__ void block_sort(uint32_t m, CmpX cmpx) {
+  uint32_t p = 1;
+  while (p < m) p <<= 1;
+  for (uint32_t k = 2; k <= p; k <<= 1) {
+    const uint32_t h = k >> 1;
+    for (uint32_t t = threadIdx.x; t < (p >> 1); t += BLOCK) {
+      const uint32_t r = t & (h - 1), b0 = (t - r) << 1;
+      const uint32_t lo = b0 + r, hi = b0 + k - 1 - r;
+      if (hi < m) cmpx(lo, hi);
+    }
+    __syncthreads();
+    for (uint32_t j = h >> 1; j >= 1; j >>= 1) {
+      for (uint32_t t = threadIdx.x; t < (p >> 1); t += BLOCK) {
+        const uint32_t r = t & (j - 1), lo = ((t - r) << 1) + r, hi = lo + j;
+        if (hi < m) cmpx(lo, hi);
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // A kernel's FIRST parameter (a struct of type T, at kernarg offset 0) read
 // from the kernarg segment through a pointer the compiler cannot see
 // through, so each use is a scalar load at the point of use instead of a

@@ -32,13 +32,11 @@
 //           mbcnt), each kept rmv's merged clock at row row_pre[key] + its rank
 // A batch with an invalid op writes no output (the write pass reads the status).
 #include <algorithm>
-#include <cstring>
-#include <string>
 
 #include "common.hpp"
 #include "compact_kernels.hpp"
+#include "device_call.hpp"
 #include "engine.hpp"
-#include "types_kernels.hpp"
 
 namespace ccrdt {
 
@@ -106,7 +104,7 @@ __device__ __forceinline__ void seg_best_scan(int64_t& sc, uint32_t& kd, int lan
 }
 
 __device__ __forceinline__ void cmp_flag(const CompactArgs& a, uint64_t bit) {
-  atomicOr(reinterpret_cast<unsigned long long*>(a.status + CMP_ST_ERR), (unsigned long long)bit);
+  atomicOr(reinterpret_cast<unsigned long long*>(a.status + ST_ERR), (unsigned long long)bit);
 }
 
 // What every wave of both kernels starts with: the batch-wide work of one
@@ -116,20 +114,20 @@ template <bool WRITE>
 __device__ __forceinline__ bool cmp_key_range(const CompactArgs& a, uint64_t& key, uint64_t& o0, uint64_t& o1) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     if (WRITE) {
-      a.status[CMP_ST_OPS] = a.o_key_ptr[a.n_keys];
-      a.status[CMP_ST_ROWS] = a.row_pre[a.n_keys];
+      a.status[ST_OPS] = a.o_key_ptr[a.n_keys];
+      a.status[ST_ROWS] = a.row_pre[a.n_keys];
     } else if (a.key_ptr[a.n_keys] != a.n_ops) {
-      cmp_flag(a, CMP_ERR_CSR);
+      cmp_flag(a, ST_ERR_SHAPE);
     }
   }
   key = (uint64_t)blockIdx.x * CMP_WAVES + (threadIdx.x >> 6);
   if (key >= a.n_keys) return false;                // (wave-uniform; the kernels have no workgroup barrier)
-  if (WRITE && a.status[CMP_ST_ERR]) return false;  // an invalid batch writes no output
+  if (WRITE && a.status[ST_ERR]) return false;  // an invalid batch writes no output
   o0 = a.key_ptr[key];
   o1 = a.key_ptr[key + 1];
   if (o0 <= o1 && o1 <= a.n_ops && o1 - o0 <= 0xFFFFFFFFull) return true;
   if (!WRITE && lane_id() == 0) {
-    cmp_flag(a, CMP_ERR_CSR);
+    cmp_flag(a, ST_ERR_SHAPE);
     a.cnt[2 * key] = a.cnt[2 * key + 1] = 0;
   }
   return false;
@@ -138,7 +136,7 @@ __device__ __forceinline__ bool cmp_key_range(const CompactArgs& a, uint64_t& ke
 // An invalid op in the chunk (count pass): flag it, count nothing for the key.
 __device__ __forceinline__ void cmp_bad_op(const CompactArgs& a, uint64_t key) {
   if (lane_id() == 0) {
-    cmp_flag(a, CMP_ERR_OP);
+    cmp_flag(a, ST_ERR_OP);
     a.cnt[2 * key] = a.cnt[2 * key + 1] = 0;
   }
 }
@@ -354,57 +352,25 @@ int compact_device(ccrdt_engine* e, bool lb, CompactArgs& a, int64_t* n_ops_out,
   Engine& E = *e;
   const uint64_t nk = (uint64_t)E.n_keys;
   CCRDT_TRY(E.cmp_cnt.ensure(nk * 8));
-  CCRDT_TRY(E.cmp_caps.ensure((nk + 1) * 8));
   CCRDT_TRY(E.cmp_rows.ensure((nk + 1) * 8));
-  CCRDT_TRY(E.cmp_part.ensure(((nk + 255) / 256 + 2) * 8));
-  CCRDT_TRY(E.cmp_status.ensure(CMP_ST_WORDS * 8));
+  CCRDT_TRY(E.scan.ensure(nk));
   a.n_keys = nk;
   a.cnt = E.cmp_cnt.as<uint32_t>();
   a.row_pre = E.cmp_rows.as<uint64_t>();
-  a.status = E.cmp_status.as<uint64_t>();
-  CCRDT_HIP(hipMemsetAsync(a.status, 0, CMP_ST_WORDS * 8, E.stream));
+  CCRDT_TRY(status_clear(E, &a.status));
   CCRDT_TRY(compact_launch_count(a, lb, E.stream));
-  uint64_t* const caps = E.cmp_caps.as<uint64_t>();
-  uint64_t* const part = E.cmp_part.as<uint64_t>();
-  CCRDT_TRY(launch_caps_scan(nullptr, a.cnt, 2, nk, caps, a.o_key_ptr, part, E.stream));
-  CCRDT_TRY(launch_caps_scan(nullptr, a.cnt + 1, 2, nk, caps, a.row_pre, part, E.stream));
+  CCRDT_TRY(E.scan.exclusive_scan(nullptr, a.cnt, 2, nk, a.o_key_ptr));
+  CCRDT_TRY(E.scan.exclusive_scan(nullptr, a.cnt + 1, 2, nk, a.row_pre));
   CCRDT_TRY(compact_launch_write(a, lb, E.stream));
-  CCRDT_HIP(hipMemcpyAsync(E.h_status, a.status, CMP_ST_WORDS * 8, hipMemcpyDeviceToHost, E.stream));
-  CCRDT_HIP(hipStreamSynchronize(E.stream));
-  uint64_t st[CMP_ST_WORDS];
-  memcpy(st, E.h_status, sizeof(st));
-  *n_ops_out = (int64_t)st[CMP_ST_OPS];
-  if (n_rows_out) *n_rows_out = (int64_t)st[CMP_ST_ROWS];
-  if (st[CMP_ST_ERR] & CMP_ERR_CSR) {
-    set_error(std::string(where) + ": key_ptr[n_keys] != n_ops, or a key's ops outside [0, n_ops)");
-    return CCRDT_EINVAL;
-  }
-  if (st[CMP_ST_ERR]) {
-    set_error(std::string(where) + (lb ? ": effect kind > 2 (no function clause)"
-                                       : ": effect kind > 3, rmv clock row out of range, or add DC rank >= n_dc"));
-    return CCRDT_EINVAL;
-  }
-  if (st[CMP_ST_OPS] > a.cap_ops || st[CMP_ST_ROWS] > a.cap_rows) {
-    set_error(std::string(where) + ": the compacted batch exceeds cap_ops or cap_rows (the totals are set)");
-    return CCRDT_ENOMEM;
-  }
-  return CCRDT_OK;
+  const char* const shape = ": key_ptr[n_keys] != n_ops, or a key's ops outside [0, n_ops)";
+  return lb ? status_finish(E, a.cap_ops, a.cap_rows, n_ops_out, n_rows_out, where, shape,
+                            ": effect kind > 2 (no function clause)")
+            : status_finish(E, a.cap_ops, a.cap_rows, n_ops_out, n_rows_out, where, shape);
 }
 
+// (a compaction's answer to an engine of another type is CCRDT_EINVAL)
 int compact_check(ccrdt_engine* e, int type, bool ok_args, const char* where) {
-  if (!e || e->type != type) {
-    set_error(std::string(where) + ": null engine, or not an engine of this CCRDT type");
-    return CCRDT_EINVAL;
-  }
-  if (!ok_args) {
-    set_error(std::string(where) + ": null arrays, or a negative count or capacity");
-    return CCRDT_EINVAL;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) {
-    set_error("hipSetDevice failed");
-    return CCRDT_EDEVICE;
-  }
-  return CCRDT_OK;
+  return guard_engine(e, {type}, CCRDT_EINVAL, where, ok_args, ": null arrays, or a negative count or capacity");
 }
 
 }  // namespace

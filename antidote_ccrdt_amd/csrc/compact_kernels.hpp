@@ -8,12 +8,6 @@ namespace ccrdt {
 
 constexpr int CMP_WAVES = 4;  // keys (waves) per workgroup
 
-// Bits of CompactArgs::status[CMP_ST_ERR].
-constexpr uint64_t CMP_ERR_OP = 1;   // a kind, clock row or DC rank out of range
-constexpr uint64_t CMP_ERR_CSR = 2;  // key_ptr[n_keys] != n_ops, or a key's range outside [0, n_ops]
-// Words of the status record the call reads back.
-constexpr int CMP_ST_ERR = 0, CMP_ST_OPS = 1, CMP_ST_ROWS = 2, CMP_ST_WORDS = 4;
-
 struct CompactArgs {
   uint64_t n_keys, n_ops, n_rows;  // n_rows: clock rows of the input (topk_rmv)
   uint32_t n_dc;
@@ -38,7 +32,7 @@ struct CompactArgs {
   // scratch
   uint32_t* cnt;      // [2 * n_keys] per key: kept ops, kept rmvs (the scans' inputs)
   uint64_t* row_pre;  // [n_keys + 1] exclusive scan of the kept rmvs: each key's first clock row
-  uint64_t* status;   // [CMP_ST_WORDS]
+  uint64_t* status;   // the call's status record (device_call.hpp); ST_ERR_SHAPE: key_ptr[n_keys] != n_ops, or a key's range outside [0, n_ops]
 };
 
 }  // namespace ccrdt

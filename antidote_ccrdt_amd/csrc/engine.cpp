@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "device_call.hpp"
 #include "engine.hpp"
 #include "trmv_kernels.hpp"
 
@@ -93,10 +94,11 @@ void ccrdt_engine::release_all() {
   for (DevBuf& d : st_nbase) d.release();
   for (DevBuf* d : {&arena, &obs_ord, &key_done, &partials, &ex_cnt, &ex, &ex_vc, &ex_key_ptr, &status, &op_pl,
                     &first_list, &ovl,
-                    &hbm_scratch, &val_cnt, &val_caps, &val_part, &val_list, &val_keys, &val_ptr, &val_id,
-                    &val_score, &cmp_cnt, &cmp_caps, &cmp_part, &cmp_rows, &cmp_status, &rpl_src, &rpl_key, &rpl_off, &st_kp,
+                    &hbm_scratch, &call_status, &val_cnt, &val_list, &val_keys, &val_ptr, &val_id,
+                    &val_score, &cmp_cnt, &cmp_rows, &rpl_src, &rpl_key, &rpl_off, &st_kp,
                     &st_kind, &st_id, &st_score, &st_dc, &st_ts, &st_rvc, &st_out_kind, &st_out_vc})
     d->release();
+  scan.release();
   wcv.release();
   release_types();
 }
@@ -184,11 +186,12 @@ int ccrdt_engine_create(int type, int64_t k, int64_t n_keys, int n_dc, int devic
       hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess ||
       hipEventCreate(&e->evk0) != hipSuccess || hipEventCreate(&e->evk1) != hipSuccess ||
       !e->create_tier_events() ||
-      hipHostMalloc((void**)&e->h_status, 256, hipHostMallocDefault) != hipSuccess) {
+      hipHostMalloc((void**)&e->h_status, H_STATUS_BYTES, hipHostMallocDefault) != hipSuccess) {
     set_error("engine_create: stream/event/pinned allocation failed");
     delete e;
     return CCRDT_EDEVICE;
   }
+  e->scan.stream = e->stream;
   if (type == CCRDT_TOPK_RMV) {  // the apply chain's kernels set up now, not in the first batches
     trmv_kernels_preload();
     trmv_wave_preload();
@@ -276,21 +279,7 @@ int ccrdt_engine_overflow_keys(ccrdt_engine* e, int slot_class, int64_t* n) {
 
 // ------------------------------------------------------------------ topk_rmv
 
-static int check_trmv(ccrdt_engine* e) {
-  if (!e) {
-    set_error("null engine");
-    return CCRDT_EINVAL;
-  }
-  if (e->type != CCRDT_TOPK_RMV) {
-    set_error("engine is not topk_rmv");
-    return CCRDT_ENOSYS;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) {
-    set_error("hipSetDevice failed");
-    return CCRDT_EDEVICE;
-  }
-  return CCRDT_OK;
-}
+static int check_trmv(ccrdt_engine* e) { return guard_engine(e, {CCRDT_TOPK_RMV}, CCRDT_ENOSYS, "topk_rmv"); }
 
 namespace {
 
@@ -359,6 +348,7 @@ struct TrmvHooks {  // (each one read where it is used, at every call, and only 
 struct TrmvStatus {
   static constexpr int TRMV_STATUS_WORDS = 2 + 2 * TRMV_N_TIERS;
   static constexpr uint64_t ALLOC = TRMV_STATUS_WORDS * 4 + 16;  // (+ the validation's scratch flag)
+  static_assert(TRMV_STATUS_WORDS * 4 <= H_STATUS_BYTES, "the words are read back into E.h_status");
   uint32_t* dev;
   uint32_t* host;
   hipStream_t stream;
@@ -591,10 +581,7 @@ int trmv_layout(TrmvRun& r) {
     CCRDT_TRY(trmv_launch_scan(a, E.partials.as<uint64_t>(),
                                reinterpret_cast<uint32_t*>(E.partials.as<uint64_t>() + nb * 3 + 3), E.stream));
     // (the exact totals size the new side)
-    CCRDT_HIP(hipMemcpyAsync(E.h_status, E.partials.as<uint64_t>() + nb * 3, 3 * sizeof(uint64_t),
-                             hipMemcpyDeviceToHost, E.stream));
-    CCRDT_HIP(hipStreamSynchronize(E.stream));
-    memcpy(r.tot, E.h_status, sizeof(r.tot));
+    CCRDT_TRY(read_back(E, r.tot, E.partials.as<uint64_t>() + nb * 3));
   }
   if (r.tot[0] >= 0xFFFFFFFFull || r.tot[1] >= 0xFFFFFFFFull || r.tot[2] >= 0xFFFFFFFFull) {
     set_error("trmv_apply: resident state would exceed 2^32 elements");
@@ -1016,9 +1003,7 @@ int ccrdt_trmv_fetch_extra(ccrdt_engine* e, ccrdt_trmv_extra* x) {
                                       E.ex.as<TrmvExtraRec>(), E.ex_vc.as<int64_t>(), nk, D,
                                       E.st_out_vc.as<int64_t>(), (int64_t)cap,
                                       E.st_out_kind.as<uint32_t>(), E.stream));
-    CCRDT_HIP(hipMemcpyAsync(E.h_status, E.st_out_kind.p, 4, hipMemcpyDeviceToHost, E.stream));
-    CCRDT_HIP(hipStreamSynchronize(E.stream));
-    memcpy(&cnt, E.h_status, 4);
+    CCRDT_TRY(read_back(E, cnt, E.st_out_kind.p));
     if (cnt <= cap) break;
     cap = cnt;  // (a second pass packs them all)
   }

@@ -3,9 +3,12 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "scan_kernels.hpp"
 #include "trmv_kernels.hpp"
 
 namespace ccrdt {
+
+constexpr size_t H_STATUS_BYTES = 256;  // the engine's pinned read-back block (h_status)
 
 // One ping-pong side of GPU-resident topk_rmv state (trmv_kernels.hpp): the
 // meta + cap arrays of meta index s and the data arrays of data index s
@@ -38,7 +41,7 @@ struct TypeBufs {
   uint64_t wc_seed = 0;   // word-hash seed; a batch that meets a collision is re-run once with a new one
   int64_t wc_checks = 0;  // the last batch's check-list records (-1: verified token by token)
   int64_t wc_route[CCRDT_WC_N_ROUTE] = {};  // the last batch's route (CCRDT_WC_ROUTE_*)
-  // scratch shared by the types
+  // scratch shared by the types (caps, part: the HBM class's needs; wordcount's owner counts and cursors)
   DevBuf caps, part, ovf_a, ovf_b, status, ex_cnt, ex, kp, stage[8];
   // HBM class of topk / leaderboard (keys beyond the LDS classes)
   DevBuf hb_off, hb_cap, hb_a, hb_b, hb_c, hb_d;
@@ -47,13 +50,13 @@ struct TypeBufs {
 // Scratch of the keyed value/1 of wordcount / worddocumentcount
 // (wc_value_kernels.hip), grown on demand; a read changes nothing else.
 struct WcValBufs {
-  DevBuf map, cnt, bytes, cur, tot, caps, part;  // key map, per-position words / bytes / cursors, totals, scan scratch
+  DevBuf map, cnt, bytes, cur, tot;              // key map, per-position words / bytes / cursors, totals
   DevBuf tiles;                                  // the tile list of the workgroup and large classes (count first)
   DevBuf idx[2], pre[2];                         // slot indices and sort prefixes, ping-pong sides of the merge passes
   DevBuf len, off;                               // lengths in sorted order and their exclusive scan
   DevBuf keys, kptr, woff, wbytes, count;        // the host variant's uploaded keys and device-side result
   void release() {
-    for (DevBuf* d : {&map, &cnt, &bytes, &cur, &tot, &caps, &part, &tiles, &idx[0], &idx[1], &pre[0], &pre[1], &len,
+    for (DevBuf* d : {&map, &cnt, &bytes, &cur, &tot, &tiles, &idx[0], &idx[1], &pre[0], &pre[1], &len,
                       &off, &keys, &kptr, &woff, &wbytes, &count})
       d->release();
   }
@@ -81,7 +84,7 @@ struct ccrdt_engine {
       if (v) (void)hipEventDestroy(v);
   }
   float last_kernel_ms = 0.f;
-  void* h_status = nullptr;  // pinned, 256 bytes
+  void* h_status = nullptr;  // pinned, H_STATUS_BYTES (read_back, device_call.hpp; the topk_rmv status block)
   bool fresh = true;         // every key == new(k); resident arrays ignored
 
   // topk_rmv
@@ -109,16 +112,20 @@ struct ccrdt_engine {
   hipEvent_t ev_ovl = nullptr;
   ccrdt::DevBuf first_list, ovl;
   ccrdt::DevBuf hbm_scratch;    // tier 4's per-wave working sets
-  // batched value/1 (value_kernels.hip): per listed key its |Observed| and the
-  // scan's scratch, the handed-on list (count first), and the host variant's
-  // uploaded keys and device-side result
-  ccrdt::DevBuf val_cnt, val_caps, val_part, val_list, val_keys, val_ptr, val_id, val_score;
+  // the call layer's (device_call.hpp): the scratch of every segment scan and
+  // the status record of the calls that size their own output
+  ccrdt::ScanScratch scan;
+  ccrdt::DevBuf call_status;
+  // batched value/1 (value_kernels.hip): per listed key its |Observed|, the
+  // handed-on list (count first), and the host variant's uploaded keys and
+  // device-side result
+  ccrdt::DevBuf val_cnt, val_list, val_keys, val_ptr, val_id, val_score;
   // device log compaction (compact_kernels.hip; both types it serves): per-key
-  // kept counts, the scans' scratch, each key's first clock row, the status record
-  ccrdt::DevBuf cmp_cnt, cmp_caps, cmp_part, cmp_rows, cmp_status;
-  // replication mode (replicate_kernels.hip; it shares the compaction's scan
-  // scratch and status record): by output position the op's source and key;
-  // the extras run's per-key output offsets
+  // kept counts, each key's first clock row
+  ccrdt::DevBuf cmp_cnt, cmp_rows;
+  // replication mode (replicate_kernels.hip; it shares the compaction's
+  // scratch): by output position the op's source and key; the extras run's
+  // per-key output offsets
   ccrdt::DevBuf rpl_src, rpl_key, rpl_off;
   int trmv_first_tier = 0;
   uint64_t last_n_ops = 0;

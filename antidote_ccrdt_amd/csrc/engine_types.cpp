@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "device_call.hpp"
 #include "engine.hpp"
 #include "types_kernels.hpp"
 
@@ -129,21 +130,9 @@ int ccrdt_engine::clone_from(const ccrdt_engine& src) {
   return CCRDT_OK;
 }
 
+// (the wordcount calls serve worddocumentcount too)
 static int check_type(ccrdt_engine* e, int type) {
-  if (!e) {
-    set_error("null engine");
-    return CCRDT_EINVAL;
-  }
-  if (e->type != type &&
-      !(type == CCRDT_WORDCOUNT && e->type == CCRDT_WORDDOCUMENTCOUNT)) {
-    set_error("operation does not match the engine's CCRDT type");
-    return CCRDT_ENOSYS;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) {
-    set_error("hipSetDevice failed");
-    return CCRDT_EDEVICE;
-  }
-  return CCRDT_OK;
+  return guard_engine(e, {type, type == CCRDT_WORDCOUNT ? CCRDT_WORDDOCUMENTCOUNT : type}, CCRDT_ENOSYS, "types engine");
 }
 
 static int check_csr(const uint64_t* key_ptr, uint64_t nk, uint64_t n) {
@@ -161,25 +150,17 @@ static int check_csr(const uint64_t* key_ptr, uint64_t nk, uint64_t n) {
 
 // The first `words` words of tb.status (at least 64 bytes), after the stream's work.
 static int read_status(ccrdt_engine* e, uint32_t* out, int words = 2) {
-  CCRDT_HIP(hipMemcpyAsync(e->h_status, e->tb.status.p, words * 4, hipMemcpyDeviceToHost, e->stream));
-  CCRDT_HIP(hipStreamSynchronize(e->stream));
-  memcpy(out, e->h_status, words * 4);
-  return CCRDT_OK;
+  return read_back(*e, out, e->tb.status.p, words * 4);
 }
 
 // segment offsets off[0..nk] of the new side: caps = cnt (stride) + ops
 static int scan_caps(ccrdt_engine* e, const uint64_t* key_ptr, const uint32_t* cnt, uint32_t stride,
                      DevBuf& off, uint64_t* total) {
   const uint64_t nk = (uint64_t)e->n_keys;
-  CCRDT_TRY(e->tb.caps.ensure((nk + 1) * 8));
-  CCRDT_TRY(e->tb.part.ensure(((nk + 255) / 256 + 2) * 8));
+  CCRDT_TRY(e->scan.ensure(nk));
   CCRDT_TRY(off.ensure((nk + 1) * 8));
-  CCRDT_TRY(launch_caps_scan(key_ptr, cnt, stride, nk, e->tb.caps.as<uint64_t>(), off.as<uint64_t>(),
-                             e->tb.part.as<uint64_t>(), e->stream));
-  CCRDT_HIP(hipMemcpyAsync(e->h_status, off.as<uint64_t>() + nk, 8, hipMemcpyDeviceToHost, e->stream));
-  CCRDT_HIP(hipStreamSynchronize(e->stream));
-  memcpy(total, e->h_status, 8);
-  return CCRDT_OK;
+  CCRDT_TRY(e->scan.exclusive_scan(key_ptr, cnt, stride, nk, off.as<uint64_t>()));
+  return read_back(*e, *total, off.as<uint64_t>() + nk);
 }
 
 // HBM class for the n keys left in `list`: per key a scratch region of
@@ -748,9 +729,7 @@ int ccrdt_lb_fetch_extra(ccrdt_engine* e, ccrdt_lb_extra* x) {
     CCRDT_TRY(lb_launch_pack_extras(T.kp.as<uint64_t>(), T.ex_cnt.as<uint32_t>(), T.ex.as<LbExtraRec>(), nk,
                                     T.stage[7].as<int64_t>(), (int64_t)cap, T.status.as<uint32_t>() + 8,
                                     e->stream));
-    CCRDT_HIP(hipMemcpyAsync(e->h_status, T.status.as<uint32_t>() + 8, 4, hipMemcpyDeviceToHost, e->stream));
-    CCRDT_HIP(hipStreamSynchronize(e->stream));
-    memcpy(&cnt, e->h_status, 4);
+    CCRDT_TRY(read_back(*e, cnt, T.status.as<uint32_t>() + 8));
     if (cnt <= cap) break;
     cap = cnt;
   }
@@ -1702,13 +1681,12 @@ int ccrdt_wc_merge_device(ccrdt_engine* e, int64_t n_words, const int64_t* d_met
   CCRDT_TRY(T.stage[0].ensure(nw * 8 + 8));
   CCRDT_TRY(T.stage[1].ensure(nw * 8 + 8));
   CCRDT_TRY(T.stage[2].ensure((nw + 1) * 8));
-  CCRDT_TRY(T.caps.ensure((nw + 1) * 8));
-  CCRDT_TRY(T.part.ensure(((nw + 255) / 256 + 2) * 8));
+  CCRDT_TRY(e->scan.ensure(nw));
   CCRDT_TRY(wc_launch_meta_split(d_meta, nw, T.stage[0].as<uint64_t>(), T.stage[1].as<int64_t>(), nullptr,
                                  e->stream));
   // word offsets: exclusive scan of the lengths (the low words of column 1)
-  CCRDT_TRY(launch_caps_scan(nullptr, nw ? (const uint32_t*)d_meta + 2 : nullptr, 6, nw, T.caps.as<uint64_t>(),
-                             T.stage[2].as<uint64_t>(), T.part.as<uint64_t>(), e->stream));
+  CCRDT_TRY(e->scan.exclusive_scan(nullptr, nw ? (const uint32_t*)d_meta + 2 : nullptr, 6, nw,
+                                   T.stage[2].as<uint64_t>()));
   std::vector<uint64_t> tot;
   CCRDT_TRY(d2h_at(tot, T.stage[2], nw, 1, e->stream));
   if (tot[0] != (uint64_t)n_bytes) {

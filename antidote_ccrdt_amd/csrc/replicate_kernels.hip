@@ -16,7 +16,7 @@
 //           op.  A window over RPL_WIN keys is searched where it lies.  The
 //           pass validates, and scatters by output position the op's source,
 //           its key and a rmv flag.
-//   scan    exclusive scan of the rmv flags (launch_caps_scan): each output
+//   scan    exclusive scan of the rmv flags (E.scan): each output
 //           rmv's clock row, numbered in output order.
 //   write   one lane per output position: the op's columns move to their
 //           place; where the merged key column steps from key a to key b the
@@ -31,13 +31,11 @@
 // wave takes 64 keys and walks their extras 64 at a time whatever key they
 // belong to, each lane ranking its record among its key's by op.
 #include <algorithm>
-#include <cstring>
-#include <string>
 
 #include "common.hpp"
+#include "device_call.hpp"
 #include "engine.hpp"
 #include "replicate_kernels.hpp"
-#include "types_kernels.hpp"
 
 namespace ccrdt {
 
@@ -98,18 +96,18 @@ __global__ __launch_bounds__(RPL_TILE) void trmv_merge_rank_kernel(MergeArgs) {
   bool isrmv = false;
   if (valid) {
     uint64_t err = 0;
-    if (k < 0 || (uint64_t)k >= ka->n_keys || (i > 0 && key[i - 1] > k)) err |= RPL_ERR_KEY;
+    if (k < 0 || (uint64_t)k >= ka->n_keys || (i > 0 && key[i - 1] > k)) err |= ST_ERR_SHAPE;
     const uint32_t kd = ka->run[a].kind[i];
     isrmv = kd >= CCRDT_TRMV_RMV;
     if (kd > CCRDT_TRMV_RMV_R) {
-      err |= RPL_ERR_OP;
+      err |= ST_ERR_OP;
     } else if (isrmv) {
       const int64_t ts = ka->run[a].ts[i];
-      if (ts < 0 || (uint64_t)ts >= ka->run[a].n_rows) err |= RPL_ERR_OP;
+      if (ts < 0 || (uint64_t)ts >= ka->run[a].n_rows) err |= ST_ERR_OP;
     } else if (ka->run[a].dc[i] >= ka->n_dc) {
-      err |= RPL_ERR_OP;
+      err |= ST_ERR_OP;
     }
-    if (err) atomicOr(reinterpret_cast<unsigned long long*>(ka->status + RPL_ST_ERR), (unsigned long long)err);
+    if (err) atomicOr(reinterpret_cast<unsigned long long*>(ka->status + ST_ERR), (unsigned long long)err);
   }
   // one lane per run: the rows of run b the tile's keys can meet, [first >= klo, first > khi)
   if (tid < R) {
@@ -173,10 +171,10 @@ __global__ __launch_bounds__(RPL_TILE) void trmv_merge_write_kernel(MergeArgs) {
   const uint32_t tid = threadIdx.x, D = ka->n_dc;
   const uint64_t N = ka->n_ops;
   if (blockIdx.x == 0 && tid == 0) {
-    ka->status[RPL_ST_OPS] = N;
-    ka->status[RPL_ST_ROWS] = ka->row_pre[N];
+    ka->status[ST_OPS] = N;
+    ka->status[ST_ROWS] = ka->row_pre[N];
   }
-  if (ka->status[RPL_ST_ERR]) return;  // an invalid merge writes nothing (the same word for every lane)
+  if (ka->status[ST_ERR]) return;  // an invalid merge writes nothing (the same word for every lane)
   {
     const auto* const tab = reinterpret_cast<const __attribute__((address_space(4))) uint64_t*>(&ka->run[0]);
     for (uint32_t j = tid; j < ka->n_runs * (uint32_t)(sizeof(RplRun) / 8); j += RPL_TILE)
@@ -242,8 +240,8 @@ __global__ __launch_bounds__(RPL_TILE) void trmv_extras_write_kernel(ExtrasRunAr
   __shared__ uint64_t cr_src[RPL_WAVES][64], cr_dst[RPL_WAVES][64];
   const int lane = lane_id(), w = threadIdx.x >> 6;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    a.status[RPL_ST_OPS] = a.ex_off[a.n_keys];
-    a.status[RPL_ST_ROWS] = a.row_off[a.n_keys];
+    a.status[ST_OPS] = a.ex_off[a.n_keys];
+    a.status[ST_ROWS] = a.row_off[a.n_keys];
   }
   const uint64_t k0 = ((uint64_t)blockIdx.x * RPL_WAVES + w) * 64, k = k0 + lane;
   const bool in = k < a.n_keys;
@@ -293,43 +291,15 @@ __global__ __launch_bounds__(RPL_TILE) void trmv_extras_write_kernel(ExtrasRunAr
 }
 
 // The status record's read-back (the call's only wait) and what it says.
-int rpl_finish(Engine& E, uint64_t* status, uint64_t cap_ops, uint64_t cap_rows, ccrdt_trmv_batch* out,
-               const char* where) {
-  CCRDT_HIP(hipMemcpyAsync(E.h_status, status, RPL_ST_WORDS * 8, hipMemcpyDeviceToHost, E.stream));
-  CCRDT_HIP(hipStreamSynchronize(E.stream));
-  uint64_t st[RPL_ST_WORDS];
-  memcpy(st, E.h_status, sizeof(st));
-  out->n_ops = (int64_t)st[RPL_ST_OPS];
-  out->n_rmv_rows = (int64_t)st[RPL_ST_ROWS];
-  if (st[RPL_ST_ERR] & RPL_ERR_KEY) {
-    set_error(std::string(where) + ": a key outside [0, n_keys), or a run whose keys decrease");
-    return CCRDT_EINVAL;
-  }
-  if (st[RPL_ST_ERR]) {
-    set_error(std::string(where) + ": effect kind > 3, rmv clock row out of range, or add DC rank >= n_dc");
-    return CCRDT_EINVAL;
-  }
-  if (st[RPL_ST_OPS] > cap_ops || st[RPL_ST_ROWS] > cap_rows) {
-    set_error(std::string(where) + ": the result exceeds cap_ops or cap_rows (the totals are set)");
-    return CCRDT_ENOMEM;
-  }
-  return CCRDT_OK;
+int rpl_finish(Engine& E, uint64_t cap_ops, uint64_t cap_rows, ccrdt_trmv_batch* out, const char* where) {
+  return status_finish(E, cap_ops, cap_rows, &out->n_ops, &out->n_rmv_rows, where,
+                       ": a key outside [0, n_keys), or a run whose keys decrease");
 }
 
+// (a replication call's answer to an engine of another type is CCRDT_EINVAL)
 int rpl_check(ccrdt_engine* e, bool ok_args, const char* where) {
-  if (!e || e->type != CCRDT_TOPK_RMV) {
-    set_error(std::string(where) + ": null engine, or not a topk_rmv engine");
-    return CCRDT_EINVAL;
-  }
-  if (!ok_args) {
-    set_error(std::string(where) + ": null arrays, a negative count or capacity, or a count out of range");
-    return CCRDT_EINVAL;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) {
-    set_error("hipSetDevice failed");
-    return CCRDT_EDEVICE;
-  }
-  return CCRDT_OK;
+  return guard_engine(e, {CCRDT_TOPK_RMV}, CCRDT_EINVAL, where, ok_args,
+                      ": null arrays, a negative count or capacity, or a count out of range");
 }
 
 }  // namespace
@@ -355,10 +325,8 @@ int ccrdt_trmv_merge_runs_device(ccrdt_engine* e, int n_runs, const ccrdt_trmv_r
   CCRDT_TRY(rpl_check(e, ok, "trmv_merge_runs_device"));
   Engine& E = *e;
   CCRDT_TRY(E.cmp_cnt.ensure(N * 4));
-  CCRDT_TRY(E.cmp_caps.ensure(N * 8));
   CCRDT_TRY(E.cmp_rows.ensure((N + 1) * 8));
-  CCRDT_TRY(E.cmp_part.ensure(((N + 255) / 256 + 2) * 8));
-  CCRDT_TRY(E.cmp_status.ensure(RPL_ST_WORDS * 8));
+  CCRDT_TRY(E.scan.ensure(N));
   CCRDT_TRY(E.rpl_src.ensure(N * 8));
   CCRDT_TRY(E.rpl_key.ensure(N * 8));
   MergeArgs a{};
@@ -376,7 +344,6 @@ int ccrdt_trmv_merge_runs_device(ccrdt_engine* e, int n_runs, const ccrdt_trmv_r
   a.mkey = E.rpl_key.as<int64_t>();
   a.rflag = E.cmp_cnt.as<uint32_t>();
   a.row_pre = E.cmp_rows.as<uint64_t>();
-  a.status = E.cmp_status.as<uint64_t>();
   a.o_key_ptr = out->key_ptr;
   a.o_kind = out->kind;
   a.o_id = out->id;
@@ -386,14 +353,13 @@ int ccrdt_trmv_merge_runs_device(ccrdt_engine* e, int n_runs, const ccrdt_trmv_r
   a.o_vc = out->rmv_vc;
   a.cap_ops = (uint64_t)cap_ops;
   a.cap_rows = (uint64_t)cap_rows;
-  CCRDT_HIP(hipMemsetAsync(a.status, 0, RPL_ST_WORDS * 8, E.stream));
+  CCRDT_TRY(status_clear(E, &a.status));
   if (tiles) hipLaunchKernelGGL(trmv_merge_rank_kernel, dim3(tiles), dim3(RPL_TILE), 0, E.stream, a);
   CCRDT_HIP(hipGetLastError());
-  CCRDT_TRY(launch_caps_scan(nullptr, a.rflag, 1, N, E.cmp_caps.as<uint64_t>(), E.cmp_rows.as<uint64_t>(),
-                             E.cmp_part.as<uint64_t>(), E.stream));
+  CCRDT_TRY(E.scan.exclusive_scan(nullptr, a.rflag, 1, N, E.cmp_rows.as<uint64_t>()));
   hipLaunchKernelGGL(trmv_merge_write_kernel, dim3((unsigned)(N / RPL_TILE + 1)), dim3(RPL_TILE), 0, E.stream, a);
   CCRDT_HIP(hipGetLastError());
-  return rpl_finish(E, a.status, a.cap_ops, a.cap_rows, out, "trmv_merge_runs_device");
+  return rpl_finish(E, a.cap_ops, a.cap_rows, out, "trmv_merge_runs_device");
 }
 
 int ccrdt_trmv_extras_run_device(ccrdt_engine* e, ccrdt_trmv_batch* out, int64_t* d_key, int64_t cap_ops,
@@ -407,11 +373,9 @@ int ccrdt_trmv_extras_run_device(ccrdt_engine* e, ccrdt_trmv_batch* out, int64_t
   const uint64_t nk = (uint64_t)E.n_keys;
   if (!(E.last_n_ops > 0 && E.ex_cnt.p) || !nk) return CCRDT_OK;  // no apply yet, or an empty one: no extras
   CCRDT_TRY(E.cmp_cnt.ensure(nk * 4));
-  CCRDT_TRY(E.cmp_caps.ensure(nk * 8));
   CCRDT_TRY(E.cmp_rows.ensure((nk + 1) * 8));
   CCRDT_TRY(E.rpl_off.ensure((nk + 1) * 8));
-  CCRDT_TRY(E.cmp_part.ensure(((nk + 255) / 256 + 2) * 8));
-  CCRDT_TRY(E.cmp_status.ensure(RPL_ST_WORDS * 8));
+  CCRDT_TRY(E.scan.ensure(nk));
   ExtrasRunArgs a{};
   a.n_keys = nk;
   a.n_dc = (uint32_t)E.n_dc;
@@ -422,7 +386,6 @@ int ccrdt_trmv_extras_run_device(ccrdt_engine* e, ccrdt_trmv_batch* out, int64_t
   a.rcnt = E.cmp_cnt.as<uint32_t>();
   a.ex_off = E.rpl_off.as<uint64_t>();
   a.row_off = E.cmp_rows.as<uint64_t>();
-  a.status = E.cmp_status.as<uint64_t>();
   a.o_key = d_key;
   a.o_kind = out->kind;
   a.o_id = out->id;
@@ -432,17 +395,15 @@ int ccrdt_trmv_extras_run_device(ccrdt_engine* e, ccrdt_trmv_batch* out, int64_t
   a.o_vc = out->rmv_vc;
   a.cap_ops = (uint64_t)cap_ops;
   a.cap_rows = (uint64_t)cap_rows;
-  CCRDT_HIP(hipMemsetAsync(a.status, 0, RPL_ST_WORDS * 8, E.stream));
+  CCRDT_TRY(status_clear(E, &a.status));
   hipLaunchKernelGGL(trmv_extras_count_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, E.stream, a);
   CCRDT_HIP(hipGetLastError());
-  uint64_t* const caps = E.cmp_caps.as<uint64_t>();
-  uint64_t* const part = E.cmp_part.as<uint64_t>();
-  CCRDT_TRY(launch_caps_scan(nullptr, a.ex_cnt, 1, nk, caps, E.rpl_off.as<uint64_t>(), part, E.stream));
-  CCRDT_TRY(launch_caps_scan(nullptr, a.rcnt, 1, nk, caps, E.cmp_rows.as<uint64_t>(), part, E.stream));
+  CCRDT_TRY(E.scan.exclusive_scan(nullptr, a.ex_cnt, 1, nk, E.rpl_off.as<uint64_t>()));
+  CCRDT_TRY(E.scan.exclusive_scan(nullptr, a.rcnt, 1, nk, E.cmp_rows.as<uint64_t>()));
   hipLaunchKernelGGL(trmv_extras_write_kernel, dim3((unsigned)((nk + RPL_TILE - 1) / RPL_TILE)), dim3(RPL_TILE), 0,
                      E.stream, a);
   CCRDT_HIP(hipGetLastError());
-  return rpl_finish(E, a.status, a.cap_ops, a.cap_rows, out, "trmv_extras_run_device");
+  return rpl_finish(E, a.cap_ops, a.cap_rows, out, "trmv_extras_run_device");
 }
 
 }  // extern "C"

@@ -14,11 +14,6 @@ constexpr int RPL_TILE = CCRDT_TRMV_MERGE_TILE;  // ops of one run per workgroup
 constexpr int RPL_WIN = 2048;                    // keys of the other runs' windows one workgroup stages in LDS at a time
 constexpr int RPL_WAVES = RPL_TILE / 64;
 
-// Bits of the status record's error word, and its words (the call reads them back).
-constexpr uint64_t RPL_ERR_OP = 1;   // a kind, clock row or DC rank out of range
-constexpr uint64_t RPL_ERR_KEY = 2;  // a key outside [0, n_keys), or a run whose keys decrease
-constexpr int RPL_ST_ERR = 0, RPL_ST_OPS = 1, RPL_ST_ROWS = 2, RPL_ST_WORDS = 4;
-
 struct RplRun {  // one ccrdt_trmv_run
   const int64_t* key;
   const uint8_t* kind;
@@ -45,7 +40,7 @@ struct MergeArgs {
   int64_t* mkey;
   uint32_t* rflag;
   const uint64_t* row_pre;  // [n_ops + 1]
-  uint64_t* status;         // [RPL_ST_WORDS]
+  uint64_t* status;         // the call's status record (device_call.hpp); ST_ERR_SHAPE: a key outside [0, n_keys), or a run whose keys decrease
   // output batch
   uint64_t* o_key_ptr;
   uint8_t* o_kind;

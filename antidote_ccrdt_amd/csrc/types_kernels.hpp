@@ -297,10 +297,7 @@ int wc_launch_cl_sum(const WcClArgs& c, hipStream_t st);
 int wc_launch_rehash(const WcSlot* old, const WcMeta* oldm, const unsigned long long* ocnt, uint64_t on,
                      const WcArgs& a, hipStream_t st);
 
-// generic segment scan: caps[k] = cnt[k * stride] + ops of key k, off = its
-// exclusive scan; need[w] of the keys an LDS class handed on
-int launch_caps_scan(const uint64_t* key_ptr, const uint32_t* cnt, uint32_t stride, uint64_t n,
-                     uint64_t* caps, uint64_t* off, uint64_t* part, hipStream_t st);
+// need[w] = cnt[k * stride] + ops of key k = list[w], the keys an LDS class handed on
 int launch_ovf_need(const uint32_t* list, uint64_t n, const uint64_t* key_ptr, const uint32_t* cnt,
                     uint32_t stride, uint64_t* need, hipStream_t st);
 

@@ -12,7 +12,7 @@
 //
 // Passes (all on the engine stream, no host wait in between):
 //   count   cnt[i] = |Observed| of keys[i]        (meta.nobs)
-//   scan    ptr = exclusive scan of cnt           (launch_caps_scan)
+//   scan    ptr = exclusive scan of cnt           (E.scan)
 //   wave    one wave per key: gather, rank by counting in LDS
 //           (|Observed| <= VAL_WAVE_MAX); larger keys go to a device list
 //   block   one workgroup per listed big key: gather, bitonic sort in LDS
@@ -21,10 +21,10 @@
 // loaded or stored, so no sentinel value is needed (every int64 is a legal Id
 // and Score) and the in-place class needs no scratch and no host sizing.
 #include <algorithm>
-#include <cstring>
 #include <string>
 
 #include "common.hpp"
+#include "device_call.hpp"
 #include "engine.hpp"
 #include "value_kernels.hpp"
 
@@ -171,30 +171,9 @@ __device__ __forceinline__ void val_cmpx(int64_t* id, int64_t* sc, uint32_t lo, 
   }
 }
 
-// Bitonic sort of m pairs by one workgroup, every compare-exchange in the
-// same direction (a stage's first step mirrors the second half of each block
-// instead of alternating directions).  Positions >= m stand for pairs that
-// rank last: an exchange with one of them never moves anything, so it is
-// skipped and the padding stays where it is.
+// The workgroup's sort of m pairs (block_sort, common.hpp).
 __device__ __forceinline__ void val_block_sort(int64_t* id, int64_t* sc, uint32_t m) {
-  uint32_t p = 1;
-  while (p < m) p <<= 1;
-  for (uint32_t k = 2; k <= p; k <<= 1) {
-    const uint32_t h = k >> 1;
-    for (uint32_t t = threadIdx.x; t < (p >> 1); t += VAL_BLOCK) {
-      const uint32_t r = t & (h - 1), b0 = (t - r) << 1;
-      const uint32_t lo = b0 + r, hi = b0 + k - 1 - r;
-      if (hi < m) val_cmpx(id, sc, lo, hi);
-    }
-    __syncthreads();
-    for (uint32_t j = h >> 1; j >= 1; j >>= 1) {
-      for (uint32_t t = threadIdx.x; t < (p >> 1); t += VAL_BLOCK) {
-        const uint32_t r = t & (j - 1), lo = ((t - r) << 1) + r, hi = lo + j;
-        if (hi < m) val_cmpx(id, sc, lo, hi);
-      }
-      __syncthreads();
-    }
-  }
+  block_sort<VAL_BLOCK>(m, [=](uint32_t lo, uint32_t hi) { val_cmpx(id, sc, lo, hi); });
 }
 
 // One workgroup per key the wave class handed on (the list and its length
@@ -254,11 +233,11 @@ __global__ __launch_bounds__(VAL_BLOCK) void value_block_kernel(ValueArgs a) {
 }
 
 template <bool LB>
-int value_launch_count(const ValueArgs& a, uint64_t* caps, uint64_t* part, hipStream_t st) {
+int value_launch_count(Engine& E, const ValueArgs& a) {
   if (a.n)
-    hipLaunchKernelGGL(value_count_kernel<LB>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(value_count_kernel<LB>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, E.stream, a);
   CCRDT_HIP(hipGetLastError());
-  return launch_caps_scan(nullptr, a.cnt, 1, a.n, caps, a.ptr, part, st);
+  return E.scan.exclusive_scan(nullptr, a.cnt, 1, a.n, a.ptr);
 }
 
 template <bool LB>
@@ -273,23 +252,8 @@ int value_launch_gather(const ValueArgs& a, hipStream_t st) {
 }
 
 int value_check(ccrdt_engine* e, bool lb, int64_t n, const char* where) {
-  if (!e) {
-    set_error("null engine");
-    return CCRDT_EINVAL;
-  }
-  if (e->type != (lb ? CCRDT_LEADERBOARD : CCRDT_TOPK_RMV)) {
-    set_error(std::string(where) + ": operation does not match the engine's CCRDT type");
-    return CCRDT_ENOSYS;
-  }
-  if (n < 0 || n > 0xFFFFFFFFll) {
-    set_error(std::string(where) + ": n must lie in [0, 2^32)");
-    return CCRDT_EINVAL;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) {
-    set_error("hipSetDevice failed");
-    return CCRDT_EDEVICE;
-  }
-  return CCRDT_OK;
+  return guard_engine(e, {lb ? CCRDT_LEADERBOARD : CCRDT_TOPK_RMV}, CCRDT_ENOSYS, where, n >= 0 && n <= 0xFFFFFFFFll,
+                      ": n must lie in [0, 2^32)");
 }
 
 // The argument block over the engine's current state and its scratch.
@@ -299,8 +263,7 @@ int value_args(ccrdt_engine* e, bool lb, int64_t n, const uint64_t* d_keys, uint
   const uint64_t un = (uint64_t)n;
   CCRDT_TRY(E.val_cnt.ensure(un * 4));
   CCRDT_TRY(E.val_list.ensure(un * 4 + 16));
-  CCRDT_TRY(E.val_caps.ensure((un + 1) * 8));
-  CCRDT_TRY(E.val_part.ensure(((un + 255) / 256 + 2) * 8));
+  CCRDT_TRY(E.scan.ensure(un));
   a = ValueArgs{};
   a.n = un;
   a.n_keys = (uint64_t)E.n_keys;
@@ -341,10 +304,10 @@ int value_device(ccrdt_engine* e, bool lb, int64_t n, const uint64_t* d_keys, ui
   ValueArgs a;
   CCRDT_TRY(value_args(e, lb, n, d_keys, d_ptr, d_id, d_score, cap, a));
   if (lb) {
-    CCRDT_TRY(value_launch_count<true>(a, e->val_caps.as<uint64_t>(), e->val_part.as<uint64_t>(), e->stream));
+    CCRDT_TRY(value_launch_count<true>(*e, a));
     return value_launch_gather<true>(a, e->stream);
   }
-  CCRDT_TRY(value_launch_count<false>(a, e->val_caps.as<uint64_t>(), e->val_part.as<uint64_t>(), e->stream));
+  CCRDT_TRY(value_launch_count<false>(*e, a));
   return value_launch_gather<false>(a, e->stream);
 }
 
@@ -355,32 +318,15 @@ int value_host(ccrdt_engine* e, bool lb, int64_t n, const uint64_t* keys, uint64
                int64_t* out_score, int64_t* total, const char* where) {
   CCRDT_TRY(value_check(e, lb, n, where));
   Engine& E = *e;
-  if (!keys && n > E.n_keys) {
-    set_error(std::string(where) + ": n > n_keys without a key list");
-    return CCRDT_EINVAL;
-  }
-  if (keys)
-    for (int64_t i = 0; i < n; ++i)
-      if (keys[i] >= (uint64_t)E.n_keys) {
-        set_error(std::string(where) + ": key index outside [0, n_keys)");
-        return CCRDT_EINVAL;
-      }
   const uint64_t un = (uint64_t)n;
-  const uint64_t* d_keys = nullptr;
-  if (keys && un) {
-    CCRDT_TRY(E.val_keys.ensure(un * 8));
-    CCRDT_TRY(h2d_staged(E, E.val_keys.p, keys, un * 8));
-    d_keys = E.val_keys.as<uint64_t>();
-  }
+  const uint64_t* d_keys;
+  CCRDT_TRY(upload_keys(E, n, keys, E.val_keys, where, &d_keys));
   CCRDT_TRY(E.val_ptr.ensure((un + 1) * 8));
   ValueArgs a;
   CCRDT_TRY(value_args(e, lb, n, d_keys, E.val_ptr.as<uint64_t>(), nullptr, nullptr, 0, a));
-  CCRDT_TRY(lb ? value_launch_count<true>(a, E.val_caps.as<uint64_t>(), E.val_part.as<uint64_t>(), E.stream)
-               : value_launch_count<false>(a, E.val_caps.as<uint64_t>(), E.val_part.as<uint64_t>(), E.stream));
-  CCRDT_HIP(hipMemcpyAsync(E.h_status, a.ptr + un, 8, hipMemcpyDeviceToHost, E.stream));
-  CCRDT_HIP(hipStreamSynchronize(E.stream));
+  CCRDT_TRY(lb ? value_launch_count<true>(E, a) : value_launch_count<false>(E, a));
   uint64_t tot = 0;
-  memcpy(&tot, E.h_status, 8);
+  CCRDT_TRY(read_back(E, tot, a.ptr + un));
   if (total) *total = (int64_t)tot;
   if (!out_ptr) return CCRDT_OK;
   CCRDT_TRY(E.val_id.ensure(tot * 8));

@@ -14,7 +14,7 @@
 //   map      map[key] = first list position naming the key   (a key list only)
 //   count    table scan: words and bytes of each listed position
 //   fix      repeats take their first occurrence's count; the totals
-//   scan     key_ptr = exclusive scan of the word counts     (launch_caps_scan)
+//   scan     key_ptr = exclusive scan of the word counts     (E.scan)
 //   scatter  table scan: slot indices into their segments, any order
 //   wave     one wave per segment: rank by counting in LDS (<= WCV_WAVE_MAX);
 //            larger segments put their tiles on a device list
@@ -24,7 +24,7 @@
 //            of runs by a binary search in the other run, so a pass is spread
 //            over the device however few segments there are
 //   len      lengths in sorted order (repeats read their first occurrence)
-//   scan     their exclusive scan: the byte offsets          (launch_caps_scan)
+//   scan     their exclusive scan: the byte offsets          (E.scan)
 //   emit     word_off, word_bytes and count of every key that fits whole
 //
 // Order: a word's sort key is its first 8 bytes, big-endian, zero-padded.
@@ -36,10 +36,10 @@
 // (the slot, in the wave class the position in the segment) only keeps the
 // comparator strict should it ever be given one word twice.
 #include <algorithm>
-#include <cstring>
 #include <string>
 
 #include "common.hpp"
+#include "device_call.hpp"
 #include "engine.hpp"
 #include "wc_value_kernels.hpp"
 
@@ -272,28 +272,9 @@ __device__ __forceinline__ void wcv_cmpx(const WcValArgs& a, uint64_t* pre, uint
   }
 }
 
-// Bitonic sort of m (sort key, slot) pairs by one workgroup, every
-// compare-exchange in the same direction; positions >= m stand for pairs that
-// come last and are never loaded or stored (value_kernels.hip val_block_sort).
+// The workgroup's sort of m (sort key, slot) pairs (block_sort, common.hpp).
 __device__ __forceinline__ void wcv_block_sort(const WcValArgs& a, uint64_t* pre, uint32_t* slot, uint32_t m) {
-  uint32_t p = 1;
-  while (p < m) p <<= 1;
-  for (uint32_t k = 2; k <= p; k <<= 1) {
-    const uint32_t h = k >> 1;
-    for (uint32_t t = threadIdx.x; t < (p >> 1); t += WCV_BLOCK) {
-      const uint32_t r = t & (h - 1), b0 = (t - r) << 1;
-      const uint32_t lo = b0 + r, hi = b0 + k - 1 - r;
-      if (hi < m) wcv_cmpx(a, pre, slot, lo, hi);
-    }
-    __syncthreads();
-    for (uint32_t j = h >> 1; j >= 1; j >>= 1) {
-      for (uint32_t t = threadIdx.x; t < (p >> 1); t += WCV_BLOCK) {
-        const uint32_t r = t & (j - 1), lo = ((t - r) << 1) + r, hi = lo + j;
-        if (hi < m) wcv_cmpx(a, pre, slot, lo, hi);
-      }
-      __syncthreads();
-    }
-  }
+  block_sort<WCV_BLOCK>(m, [&a, pre, slot](uint32_t lo, uint32_t hi) { wcv_cmpx(a, pre, slot, lo, hi); });
 }
 
 // One workgroup per listed tile (the list and its length live on the
@@ -430,23 +411,8 @@ __global__ __launch_bounds__(256) void wcv_emit_kernel(WcValArgs a) {
 unsigned wcv_grid(uint64_t n, uint64_t per) { return (unsigned)((n + per - 1) / per); }
 
 int wcv_check(ccrdt_engine* e, int64_t n, const char* where) {
-  if (!e) {
-    set_error("null engine");
-    return CCRDT_EINVAL;
-  }
-  if (e->type != CCRDT_WORDCOUNT && e->type != CCRDT_WORDDOCUMENTCOUNT) {
-    set_error(std::string(where) + ": operation does not match the engine's CCRDT type");
-    return CCRDT_ENOSYS;
-  }
-  if (n < 0 || n >= 0xFFFFFFFFll) {
-    set_error(std::string(where) + ": n must lie in [0, 2^32 - 1)");
-    return CCRDT_EINVAL;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) {
-    set_error("hipSetDevice failed");
-    return CCRDT_EDEVICE;
-  }
-  return CCRDT_OK;
+  return guard_engine(e, {CCRDT_WORDCOUNT, CCRDT_WORDDOCUMENTCOUNT}, CCRDT_ENOSYS, where, n >= 0 && n < 0xFFFFFFFFll,
+                      ": n must lie in [0, 2^32 - 1)");
 }
 
 bool wcv_fresh(const Engine& E) { return E.fresh || !E.tb.t_slots[E.tb.tcur]; }
@@ -466,8 +432,7 @@ int wcv_args(Engine& E, int64_t n, const uint64_t* d_keys, uint64_t* d_key_ptr, 
   CCRDT_TRY(V.bytes.ensure(un * 8));
   CCRDT_TRY(V.cur.ensure(un * 4));
   CCRDT_TRY(V.tot.ensure(32));
-  CCRDT_TRY(V.caps.ensure((un + 1) * 8));
-  CCRDT_TRY(V.part.ensure(((un + 255) / 256 + 2) * 8));
+  CCRDT_TRY(E.scan.ensure(un));
   a = WcValArgs{};
   a.n = un;
   a.n_keys = (uint64_t)E.n_keys;
@@ -509,7 +474,7 @@ int wcv_launch_count(Engine& E, const WcValArgs& a) {
     hipLaunchKernelGGL(wcv_fix_kernel, dim3(wcv_grid(a.n, 256)), dim3(256), 0, st, a);
   }
   CCRDT_HIP(hipGetLastError());
-  return launch_caps_scan(nullptr, a.cnt, 1, a.n, E.wcv.caps.as<uint64_t>(), a.key_ptr, E.wcv.part.as<uint64_t>(), st);
+  return E.scan.exclusive_scan(nullptr, a.cnt, 1, a.n, a.key_ptr);
 }
 
 // The order passes' scratch for at most n_sort words.
@@ -527,8 +492,7 @@ int wcv_order_scratch(Engine& E, WcValArgs& a, uint64_t n_sort) {
   CCRDT_TRY(V.tiles.ensure((n_sort / WCV_WAVE_MAX + 16) * sizeof(WcValTile)));
   CCRDT_TRY(V.len.ensure(n_sort * 4));
   CCRDT_TRY(V.off.ensure((n_sort + 1) * 8));
-  CCRDT_TRY(V.caps.ensure((std::max(n_sort, a.n) + 1) * 8));
-  CCRDT_TRY(V.part.ensure(((std::max(n_sort, a.n) + 255) / 256 + 2) * 8));
+  CCRDT_TRY(E.scan.ensure(std::max(n_sort, a.n)));
   a.tiles = V.tiles.as<WcValTile>();
   a.len = V.len.as<uint32_t>();
   a.off = V.off.as<uint64_t>();
@@ -554,8 +518,7 @@ int wcv_launch_order(Engine& E, const WcValArgs& a) {
     hipLaunchKernelGGL(wcv_merge_kernel, dim3(tile_grid), dim3(WCV_BLOCK), 0, st, a, k);
   hipLaunchKernelGGL(wcv_len_kernel, dim3(wcv_grid(n_sort, 256)), dim3(256), 0, st, a);
   CCRDT_HIP(hipGetLastError());
-  CCRDT_TRY(launch_caps_scan(nullptr, a.len, 1, n_sort, V.caps.as<uint64_t>(), V.off.as<uint64_t>(),
-                             V.part.as<uint64_t>(), st));
+  CCRDT_TRY(E.scan.exclusive_scan(nullptr, a.len, 1, n_sort, V.off.as<uint64_t>()));
   hipLaunchKernelGGL(wcv_emit_kernel, dim3(wcv_grid(n_sort, 256)), dim3(256), 0, st, a);
   CCRDT_HIP(hipGetLastError());
   return CCRDT_OK;
@@ -568,31 +531,15 @@ int wcv_host(ccrdt_engine* e, int64_t n, const uint64_t* keys, uint64_t* out_key
              uint8_t* out_bytes, int64_t* out_count, int64_t* n_words, int64_t* n_bytes, const char* where) {
   Engine& E = *e;  // (checked by the caller: wcv_check)
   WcValBufs& V = E.wcv;
-  if (!keys && n > E.n_keys) {
-    set_error(std::string(where) + ": n > n_keys without a key list");
-    return CCRDT_EINVAL;
-  }
-  if (keys)
-    for (int64_t i = 0; i < n; ++i)
-      if (keys[i] >= (uint64_t)E.n_keys) {
-        set_error(std::string(where) + ": key index outside [0, n_keys)");
-        return CCRDT_EINVAL;
-      }
   const uint64_t un = (uint64_t)n;
-  const uint64_t* d_keys = nullptr;
-  if (keys && un) {
-    CCRDT_TRY(V.keys.ensure(un * 8));
-    CCRDT_TRY(h2d_staged(E, V.keys.p, keys, un * 8));
-    d_keys = V.keys.as<uint64_t>();
-  }
+  const uint64_t* d_keys;
+  CCRDT_TRY(upload_keys(E, n, keys, V.keys, where, &d_keys));
   CCRDT_TRY(V.kptr.ensure((un + 1) * 8));
   WcValArgs a;
   CCRDT_TRY(wcv_args(E, n, d_keys, V.kptr.as<uint64_t>(), nullptr, a));
   CCRDT_TRY(wcv_launch_count(E, a));
-  CCRDT_HIP(hipMemcpyAsync(E.h_status, a.totals, 16, hipMemcpyDeviceToHost, E.stream));
-  CCRDT_HIP(hipStreamSynchronize(E.stream));
   uint64_t tot[2] = {0, 0};
-  memcpy(tot, E.h_status, 16);
+  CCRDT_TRY(read_back(E, tot, a.totals));
   if (n_words) *n_words = (int64_t)tot[0];
   if (n_bytes) *n_bytes = (int64_t)tot[1];
   if (!out_key_ptr) return CCRDT_OK;

@@ -223,28 +223,41 @@ class DeviceArray:
             pass
 
 
-class DeviceTrmvBatch:
+class _DeviceTrmvColumns:
+    """Topk_rmv ops resident in HBM: one device buffer per name of COLUMNS,
+    which are the pointer fields of the ctypes struct CSTRUCT, in its order."""
+    COLUMNS: tuple = ()
+    CSTRUCT = None
+
+    def _set(self, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None) -> None:
+        self.n_ops, self.n_rmv, self.bufs = int(n_ops), int(n_rmv), bufs
+        self.n_rmv_ops = n_rmv_ops  # how many ops are rmvs (they may share clock rows); None: not known
+        self.c = self.CSTRUCT(self.n_ops, self.n_rmv, *[bufs[n].p for n in self.COLUMNS])
+
+    @classmethod
+    def from_buffers(cls, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None = None):
+        """A batch or run over device buffers that already hold it: bufs maps
+        every name of COLUMNS to a buffer with a device pointer `.p` (a
+        DeviceArray), which the object owns from here on.  n_rmv_ops: how many
+        of its ops are rmvs, where the producer knows."""
+        d = cls.__new__(cls)
+        d._set(n_ops, n_rmv, bufs, n_rmv_ops)
+        return d
+
+    def close(self):
+        for d in self.bufs.values():
+            d.close()
+
+
+class DeviceTrmvBatch(_DeviceTrmvColumns):
     """A TrmvBatch resident in HBM (for ccrdt_trmv_apply_device)."""
     COLUMNS = ("key_ptr", "kind", "id", "score", "dc", "ts", "rmv_vc")
+    CSTRUCT = _lib.TrmvOps
 
     def __init__(self, b: TrmvBatch):
         b = b.normalized()
         self._set(b.n_ops, int(b.rmv_vc.shape[0]), {f.name: DeviceArray(getattr(b, f.name)) for f in fields(b)},
                   int(np.count_nonzero(b.kind >= _lib.TRMV_RMV)))
-
-    def _set(self, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None) -> None:
-        self.n_ops, self.n_rmv, self.bufs = int(n_ops), int(n_rmv), bufs
-        self.n_rmv_ops = n_rmv_ops  # how many ops are rmvs (they may share clock rows); None: not known
-        self.c = _lib.TrmvOps(self.n_ops, self.n_rmv, *[bufs[n].p for n in self.COLUMNS])
-
-    @classmethod
-    def from_buffers(cls, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None = None) -> "DeviceTrmvBatch":
-        """A batch over device buffers that already hold it: bufs maps every
-        name of COLUMNS to a DeviceArray, which the batch owns from here on.
-        n_rmv_ops: how many of its ops are rmvs, where the producer knows."""
-        db = cls.__new__(cls)
-        db._set(n_ops, n_rmv, bufs, n_rmv_ops)
-        return db
 
     def to_host(self, n_dc: int) -> TrmvBatch:
         """The batch copied back to the host (n_ops ops, n_rmv clock rows of n_dc)."""
@@ -252,10 +265,6 @@ class DeviceTrmvBatch:
         return TrmvBatch(b["key_ptr"].to_host(np.uint64), b["kind"].to_host(np.uint8, n), b["id"].to_host(np.int64, n),
                          b["score"].to_host(np.int64, n), b["dc"].to_host(np.uint8, n), b["ts"].to_host(np.int64, n),
                          b["rmv_vc"].to_host(np.int64, r * n_dc).reshape(r, n_dc))
-
-    def close(self):
-        for d in self.bufs.values():
-            d.close()
 
 
 @dataclass
@@ -278,38 +287,21 @@ class TrmvRun:
         return cls(key, b.kind, b.id, b.score, b.dc, b.ts, b.rmv_vc)
 
 
-class DeviceTrmvRun:
+class DeviceTrmvRun(_DeviceTrmvColumns):
     """A TrmvRun resident in HBM (for ccrdt_trmv_merge_runs_device)."""
     COLUMNS = ("key", "kind", "id", "score", "dc", "ts", "rmv_vc")
+    CSTRUCT = _lib.TrmvRun
     DTYPES = (np.int64, np.uint8, np.int64, np.int64, np.uint8, np.int64, np.int64)
 
     def __init__(self, r: TrmvRun):
         cols = {n: DeviceArray(_c(getattr(r, n), dt)) for n, dt in zip(self.COLUMNS, self.DTYPES)}
         self._set(int(r.kind.shape[0]), int(r.rmv_vc.shape[0]), cols, int(np.count_nonzero(r.kind >= _lib.TRMV_RMV)))
 
-    def _set(self, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None) -> None:
-        self.n_ops, self.n_rmv, self.bufs = int(n_ops), int(n_rmv), bufs
-        self.n_rmv_ops = n_rmv_ops  # how many ops are rmvs (they may share clock rows); None: not known
-        self.c = _lib.TrmvRun(self.n_ops, self.n_rmv, *[bufs[n].p for n in self.COLUMNS])
-
-    @classmethod
-    def from_buffers(cls, n_ops: int, n_rmv: int, bufs: dict, n_rmv_ops: int | None = None) -> "DeviceTrmvRun":
-        """A run over device buffers that already hold it: bufs maps every name
-        of COLUMNS to a buffer with a device pointer `.p` (a DeviceArray), which
-        the run owns from here on."""
-        dr = cls.__new__(cls)
-        dr._set(n_ops, n_rmv, bufs, n_rmv_ops)
-        return dr
-
     def to_host(self, n_dc: int) -> TrmvRun:
         """The run copied back to the host (n_ops ops, n_rmv clock rows of n_dc)."""
         n, r = self.n_ops, self.n_rmv
         cols = [self.bufs[c].to_host(dt, n) for c, dt in zip(self.COLUMNS[:-1], self.DTYPES)]
         return TrmvRun(*cols, self.bufs["rmv_vc"].to_host(np.int64, r * n_dc).reshape(r, n_dc))
-
-    def close(self):
-        for d in self.bufs.values():
-            d.close()
 
 
 class _Engine:
@@ -369,6 +361,12 @@ class _Engine:
         out = np.empty(n.value, np.uint32)
         check(lib.ccrdt_engine_handed_on(self.h, tier, ptr(out), n.value, C.byref(n)), "handed_on")
         return out
+
+    def _op_bufs(self, names, cap_ops: int, cap_rows: int, alloc) -> dict:
+        """Uninitialised output buffers of a device call: cap_ops ops, cap_rows clock rows."""
+        size = {"key_ptr": 8 * (self.n_keys + 1), "key": 8 * cap_ops, "kind": cap_ops, "id": 8 * cap_ops,
+                "score": 8 * cap_ops, "dc": cap_ops, "ts": 8 * cap_ops, "rmv_vc": 8 * cap_rows * self.n_dc}
+        return {n: alloc(size[n]) for n in names}
 
     def _values(self, name: str, keys):
         """ccrdt_<name>_value over `keys` (None: every key): (ptr uint64[n + 1],
@@ -463,25 +461,11 @@ class TopkRmvEngine(_Engine):
         cap_ops = db.n_ops if cap_ops is None else int(cap_ops)
         if cap_rows is None:
             cap_rows = db.n_ops if db.n_rmv_ops is None else db.n_rmv_ops
-        size = {"key_ptr": 8 * (self.n_keys + 1), "kind": cap_ops, "id": 8 * cap_ops, "score": 8 * cap_ops,
-                "dc": cap_ops, "ts": 8 * cap_ops, "rmv_vc": 8 * cap_rows * self.n_dc}
-        bufs = {n: DeviceArray.empty(size[n]) for n in DeviceTrmvBatch.COLUMNS}
+        bufs = self._op_bufs(DeviceTrmvBatch.COLUMNS, cap_ops, int(cap_rows), DeviceArray.empty)
         co = _lib.TrmvOps(0, 0, *[bufs[n].p for n in DeviceTrmvBatch.COLUMNS])
-        try:
-            check(lib.ccrdt_trmv_compact_device(self.h, C.byref(db.c), C.byref(co), cap_ops, cap_rows),
-                  "trmv_compact_device")
-        except _lib.CcrdtError as err:
-            err.totals = (int(co.n_ops), int(co.n_rmv_rows))
-            for d in bufs.values():
-                d.close()
-            raise
+        self._sized_call(lib.ccrdt_trmv_compact_device, "trmv_compact_device", co, bufs, C.byref(db.c), C.byref(co),
+                         cap_ops, int(cap_rows))
         return DeviceTrmvBatch.from_buffers(co.n_ops, co.n_rmv_rows, bufs, n_rmv_ops=co.n_rmv_rows)
-
-    def _op_bufs(self, names, cap_ops: int, cap_rows: int, alloc) -> dict:
-        """Uninitialised output buffers of a device call: cap_ops ops, cap_rows clock rows."""
-        size = {"key_ptr": 8 * (self.n_keys + 1), "key": 8 * cap_ops, "kind": cap_ops, "id": 8 * cap_ops,
-                "score": 8 * cap_ops, "dc": cap_ops, "ts": 8 * cap_ops, "rmv_vc": 8 * cap_rows * self.n_dc}
-        return {n: alloc(size[n]) for n in names}
 
     def _sized_call(self, fn, where: str, co, bufs: dict, *args) -> None:
         """A device call that sets co.n_ops / co.n_rmv_rows: an error frees the

@@ -184,8 +184,7 @@ class LeaderboardEngine(_Engine):
         compact_lb's result, bit for bit, as a new device batch (n = the
         compacted op count) that apply_device takes as it is."""
         from .engine import DeviceArray
-        size = {"key_ptr": 8 * (self.n_keys + 1), "kind": d.n, "id": 8 * d.n, "score": 8 * d.n}
-        out = DeviceBatch.from_buffers(0, {k: DeviceArray.empty(v) for k, v in size.items()})
+        out = DeviceBatch.from_buffers(0, self._op_bufs(("key_ptr", "kind", "id", "score"), d.n, 0, DeviceArray.empty))
         co = _lib.LbOps(0, out["key_ptr"], out["kind"], out["id"], out["score"])
         ci = _lib.LbOps(d.n, d["key_ptr"], d["kind"], d["id"], d["score"])
         try:
