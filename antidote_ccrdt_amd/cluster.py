@@ -59,12 +59,15 @@ class Shard:
     op_index: np.ndarray  # global op index of each local op
 
 
-def route(batch: TrmvBatch, keys: np.ndarray) -> Shard:
-    """The sub-batch of `keys` (global ids): each key's ops keep their stream
-    order; rmv ops get their clock rows re-numbered into the sub-batch."""
+def route(batch: TrmvBatch, keys: np.ndarray, drop=()) -> Shard:
+    """The sub-batch of `keys` (global ids) without the ops of the keys at the
+    positions `drop` of `keys` (their key ranges left empty): each key's ops
+    keep their stream order; rmv ops get their clock rows re-numbered into the
+    sub-batch.  The one place that takes ops out of a batch."""
     kp = np.asarray(batch.key_ptr, dtype=np.int64)
     keys = np.asarray(keys, dtype=np.int64)
     starts, lens = kp[keys], kp[keys + 1] - kp[keys]
+    lens[np.asarray(drop, np.int64)] = 0
     lkp = np.zeros(len(keys) + 1, np.int64)
     np.cumsum(lens, out=lkp[1:])
     n = int(lkp[-1])
@@ -81,7 +84,12 @@ def route(batch: TrmvBatch, keys: np.ndarray) -> Shard:
     return Shard(keys, sub, op_index)
 
 
-def _apply_keycap(engine, batch, host_keys: set, key_ids=None):
+def _drop_keys(batch: TrmvBatch, drop: np.ndarray) -> TrmvBatch:
+    """The batch without the ops of the (local) keys in `drop`."""
+    return route(batch, np.arange(batch.key_ptr.shape[0] - 1), drop).batch
+
+
+def _apply_keycap(engine, batch, host_keys: set, key_ids=None) -> TrmvExtra:
     """engine.apply(batch, want_extra=True), with CCRDT_EKEYCAP turned into a
     record: the batch committed for every key but the listed ones, whose
     extras are in err.extra; their (global) ids join host_keys.  The caller
@@ -89,33 +97,14 @@ def _apply_keycap(engine, batch, host_keys: set, key_ids=None):
     (raise_host_keys), so no rank leaves a collective sequence early."""
     from ._lib import KeyCapacityError
     try:
-        return engine.apply(batch, want_extra=True)
+        x = engine.apply(batch, want_extra=True)
     except KeyCapacityError as err:
         keys = np.asarray(err.keys if err.keys is not None else [], np.int64)
         if key_ids is not None:
             keys = np.asarray(key_ids, np.int64)[keys]
         host_keys.update(int(k) for k in keys)
-        return err.extra
-
-
-def _drop_keys(batch: TrmvBatch, drop: np.ndarray) -> TrmvBatch:
-    """The batch without the ops of the (local) keys in `drop` (their key
-    ranges left empty; rmv clock rows renumbered)."""
-    kp = np.asarray(batch.key_ptr, np.int64)
-    keep = np.ones(batch.n_ops, bool)
-    for k in drop:
-        keep[kp[k]:kp[k + 1]] = False
-    lens = np.diff(kp)
-    lens[drop] = 0
-    nkp = np.zeros_like(kp)
-    np.cumsum(lens, out=nkp[1:])
-    kind = batch.kind[keep]
-    ts = np.array(batch.ts[keep], np.int64)
-    rm = kind >= 2
-    rows = ts[rm]
-    ts[rm] = np.arange(rows.shape[0], dtype=np.int64)
-    return TrmvBatch(nkp.astype(np.uint64), kind, batch.id[keep], batch.score[keep], batch.dc[keep], ts,
-                     np.ascontiguousarray(batch.rmv_vc[rows], dtype=np.int64))
+        x = err.extra
+    return TrmvExtra(**x) if isinstance(x, dict) else x
 
 
 def raise_host_keys(mine, extra=None, coll=None) -> None:
@@ -127,16 +116,10 @@ def raise_host_keys(mine, extra=None, coll=None) -> None:
     (INTEGRATION.md): the drivers leave their ops out of later batches.
     The keys travel on the collective's device (RCCL takes device tensors
     only)."""
-    import torch
-
     from ._lib import EKEYCAP, KeyCapacityError
     mine = np.array(sorted(int(k) for k in mine), np.int64)
     if coll is not None and coll.world > 1:
-        t = torch.from_numpy(mine)
-        dev = getattr(coll, "device", None)
-        if dev is not None:
-            t = t.to(dev)
-        parts = coll.all_gather_v(t)
+        parts = coll.all_gather_v(_wire_in(coll, mine))
         allk = np.unique(np.concatenate([p.cpu().numpy() for p in parts])) if parts else mine
     else:
         allk = mine
@@ -164,11 +147,26 @@ def _dist():
     return dist if dist.is_available() and dist.is_initialized() else None
 
 
+def _rank_world(rank, world):
+    """(rank, world), each defaulting to the process group's (one rank without one)."""
+    dist = _dist()
+    return (rank if rank is not None else (dist.get_rank() if dist else 0),
+            world if world is not None else (dist.get_world_size() if dist else 1))
+
+
 def _device_for(dist):
     import torch
     if dist is not None and dist.get_backend() == "nccl":
         return torch.device("cuda", torch.cuda.current_device())
     return torch.device("cpu")
+
+
+def _wire_in(coll, a: np.ndarray):
+    """A host array as a tensor where the collective takes it (RCCL: on its device)."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    dev = getattr(coll, "device", None)
+    return t.to(dev) if dev is not None else t
 
 
 EXTRA_COLS = 6  # op, kind, id, score, dc, ts (then n_dc clock columns)
@@ -189,31 +187,16 @@ def pack_extras(x: TrmvExtra, op_index: np.ndarray) -> np.ndarray:
     return rows
 
 
-def all_gather_rows(rows: np.ndarray, tag: int = 0):
-    """All-gather variable-length int64 row blocks (sizes first, then one
-    padded all_gather), concatenated in rank order.  `tag`: a per-rank count
-    that rides the sizes' gather; returns (rows, sum of the tags)."""
-    import torch
-    dist = _dist()
-    if dist is None:
-        return rows, int(tag)
-    world = dist.get_world_size()
-    dev = _device_for(dist)
-    width = rows.shape[1]
-    n = torch.tensor([rows.shape[0], int(tag)], dtype=torch.int64, device=dev)
-    ns = [torch.zeros_like(n) for _ in range(world)]
-    dist.all_gather(ns, n)
-    hv = torch.stack(ns).cpu().numpy()
-    counts, tags = [int(c) for c in hv[:, 0]], int(hv[:, 1].sum())
-    cap = max(max(counts), 1)
-    if not sum(counts):
-        return rows[:0], tags
-    buf = torch.zeros((cap, width), dtype=torch.int64, device=dev)
-    if rows.shape[0]:
-        buf[: rows.shape[0]] = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
-    outs = [torch.zeros_like(buf) for _ in range(world)]
-    dist.all_gather(outs, buf)
-    return np.concatenate([o[:c].cpu().numpy() for o, c in zip(outs, counts)], axis=0), tags
+def all_gather_rows(rows: np.ndarray, tag: int = 0, coll=None):
+    """All-gather variable-length int64 row blocks with a per-rank word `tag`
+    riding the sizes' gather (TorchCollective.all_gather_v: sizes, then one
+    padded gather when any rank has rows): [(rows, tag) of rank 0, ...].
+    coll None: the global process group's, or this rank alone without one."""
+    coll = coll if coll is not None else (TorchCollective() if _dist() is not None else None)
+    if coll is None:
+        return [(rows, int(tag))]
+    parts, tags = coll.all_gather_v(_wire_in(coll, rows), tag=int(tag))
+    return [(p.cpu().numpy(), t) for p, t in zip(parts, tags)]
 
 
 def all_reduce_max(v: np.ndarray) -> np.ndarray:
@@ -397,8 +380,7 @@ class ShardedTopkRmv:
     def __init__(self, n_keys: int, k: int = 100, n_dc: int = 8, rank: int | None = None,
                  world: int | None = None, engine_factory=None, device: int = 0, coll=None):
         dist = _dist()
-        self.rank = rank if rank is not None else (dist.get_rank() if dist else 0)
-        self.world = world if world is not None else (dist.get_world_size() if dist else 1)
+        self.rank, self.world = _rank_world(rank, world)
         self.n_keys, self.k, self.n_dc = n_keys, k, n_dc
         self.keys = owned_keys(n_keys, self.world, self.rank)
         self.on_device = engine_factory is None
@@ -418,15 +400,9 @@ class ShardedTopkRmv:
 
     def route(self, batch: TrmvBatch) -> Shard:
         """This rank's sub-batch of a global batch (host-path keys' ops left out)."""
-        sh = route(batch, self.keys)
-        if self.host_keys:
-            drop = np.nonzero(np.isin(self.keys, np.array(sorted(self.host_keys), np.int64)))[0]
-            kp = np.asarray(sh.batch.key_ptr, np.int64)
-            keep = np.ones(sh.batch.n_ops, bool)
-            for k in drop:
-                keep[kp[k]:kp[k + 1]] = False
-            sh = Shard(sh.keys, _drop_keys(sh.batch, drop), sh.op_index[keep])
-        return sh
+        if not self.host_keys:
+            return route(batch, self.keys)
+        return route(batch, self.keys, np.nonzero(np.isin(self.keys, np.array(sorted(self.host_keys), np.int64)))[0])
 
     def apply(self, batch: TrmvBatch) -> np.ndarray:
         """update/2 over this rank's keys of a global batch on the engine's
@@ -434,10 +410,7 @@ class ShardedTopkRmv:
         op index first).  Over-capacity keys join host_keys."""
         self._vc = None
         sh = self.route(batch)
-        x = _apply_keycap(self.engine, sh.batch, self.host_keys, self.keys)
-        if isinstance(x, dict):
-            x = TrmvExtra(**x)
-        return pack_extras(x, sh.op_index)
+        return pack_extras(_apply_keycap(self.engine, sh.batch, self.host_keys, self.keys), sh.op_index)
 
     def apply_device(self, db, op_index=None) -> int:
         """update/2 over a device-resident sub-batch (DeviceTrmvBatch, CSR over
@@ -472,19 +445,18 @@ class ShardedTopkRmv:
         self._vc = None
         local_err = None
         try:
-            sh = self.route(batch)
             if self.on_device:
                 import torch
 
                 from .engine import DeviceTrmvBatch
+                sh = self.route(batch)
                 db = DeviceTrmvBatch(sh.batch)
                 try:
                     self.apply_device(db, torch.from_numpy(sh.op_index).to(self.xchg.dev))
                 finally:
                     db.close()
             else:
-                rows = pack_extras(TrmvExtra(**_as_dict(_apply_keycap(self.engine, sh.batch, self.host_keys,
-                                                                      self.keys))), sh.op_index)
+                rows = self.apply(batch)
                 self.xchg.fill_from_rows(rows, self._local_vc(), len(self.host_keys - self.reported))
         except Exception as e:  # noqa: BLE001 - re-raised on every rank after the exchange
             local_err = e
@@ -540,33 +512,64 @@ class ShardedTopkRmv:
         return self.engine.values(local.astype(np.uint64))
 
 
-def _as_dict(x):
-    if isinstance(x, dict):
-        return x
-    return {f: getattr(x, f) for f in x.__dataclass_fields__}
-
-
-def all_reduce_sum(v: int) -> int:
-    import torch
-    dist = _dist()
-    if dist is None:
-        return int(v)
-    t = torch.tensor([int(v)], dtype=torch.int64, device=_device_for(dist))
-    dist.all_reduce(t)
-    return int(t.item())
-
-
 # ------------------------------------------------------- replication mode
 # Each rank is one DC replica holding the whole keyspace (SURVEY §8(e),
 # BASELINE configs[3]).  A step: every rank applies the effects it originates
 # (update/2 at the origin, src/antidote_ccrdt_leaderboard.erl:128-134,
 # src/antidote_ccrdt_topk_rmv.erl:140-148) and keeps the extra effects that
 # returns (:282-284; topk_rmv :236,294) as effects it originates too; the
-# effect rows of all ranks are all-gathered, and every rank applies the
+# messages of all ranks are all-gathered, and every rank applies the
 # effects of the OTHER origins in canonical order -- by key, then origin
 # rank, then the origin's sequence number.  Applying remote effects can
 # return extras again; they go out in the next round, until a round gathers
-# nothing.  Rows are int64: origin, seq, key, then the effect's fields.
+# nothing.  The step is written once (_replicate); a flavour is a replica
+# class: the host-row protocol (_Replica: int64 rows origin, seq, key, then
+# the effect's fields) and the two device ones (_DeviceReplica: runs).
+_MSG_FAIL = 1 << 32  # in a message's word 0 / a host-row message's tag: the sender's apply raised
+
+
+def _replicate(replicas, batches, gather=None, max_rounds: int = 64) -> int:
+    """One replication step of `replicas` (origin o = replicas[o] when this
+    process holds them all; one replica per process otherwise); returns the
+    number of delivery rounds.  `gather` takes this process's one message to
+    every rank's (a collective, parts[o] = origin o's); None: the process
+    holds every replica and their messages are the gather.
+
+    A replica has originate(batch) -> message, deliver(round) -> message,
+    failed_message(), and read(parts) -> (ranks that sent a failed message,
+    the round to deliver or None when nothing was gathered): the one host
+    look at a gather, shared by the replicas of a process.
+
+    Failure: under a collective every rank issues the same collectives.  A
+    rank whose originate or deliver raises sends failed_message(), takes part
+    in the gather, and then every rank raises PeerStepError (the failing
+    rank's exception chained).  One process has no peer to strand: the
+    exception propagates, a KeyCapacityError (the batch committed for every
+    other key) once every replica has applied the round."""
+    from ._lib import KeyCapacityError
+    waits = Exception if gather is not None else KeyCapacityError
+
+    def each(method: str, args):
+        outs, err = [], None
+        for r, a in zip(replicas, args):
+            try:
+                outs.append(getattr(r, method)(a))
+            except waits as e:  # raised below, or by every rank after the gather
+                err = err or e
+                outs.append(r.failed_message())
+        if err is not None and gather is None:
+            raise err
+        return outs, err
+    outs, err = each("originate", batches)
+    for rounds in range(max_rounds):
+        failed, rnd = replicas[0].read(gather(outs[0]) if gather is not None else outs)
+        if failed:
+            raise PeerStepError(failed) from err
+        if rnd is None:
+            return rounds
+        outs, err = each("deliver", [rnd] * len(replicas))
+    raise RuntimeError("replication did not quiesce")
+
 
 @dataclass
 class _TrmvCodec:
@@ -605,8 +608,6 @@ class _TrmvCodec:
         (origin/seq left for the caller)."""
         b = self.batch_of_rows(r)
         x = _apply_keycap(engine, b, self.host_keys)
-        if isinstance(x, dict):
-            x = TrmvExtra(**x)
         sel = np.nonzero(x.kind != 255)[0]
         out = np.zeros((sel.shape[0], self.COLS + self.n_dc), np.int64)
         out[:, 2] = r[sel, 2]
@@ -648,10 +649,30 @@ def canonical(rows: np.ndarray) -> np.ndarray:
     return rows[np.lexsort((rows[:, 1], rows[:, 0], rows[:, 2]))] if rows.shape[0] else rows
 
 
+def _report_host_keys(replicas, result, coll=None) -> None:
+    """Every listed replica's keys handed to the host path (CCRDT_EKEYCAP)
+    since the last report, reported once: raise_host_keys over `coll`."""
+    new = set()
+    for r in replicas:
+        hk = getattr(r.codec, "host_keys", None)
+        if hk is not None:
+            new |= hk - r.codec.reported
+            r.codec.reported |= hk
+    raise_host_keys(new, result, coll)
+
+
 class _Replica:
+    """A replica of the host-row protocol.  Its message is (rows, tag): the
+    tag word rides the sizes' gather (all_gather_rows) and holds the replica's
+    count of keys handed to the host path and not yet reported, and
+    _MSG_FAIL."""
+
     def __init__(self, codec, engine, rank, world):
-        self.codec, self.engine, self.rank, self.world = codec, engine, rank, world
+        self.codec, self.engine = codec, engine
+        self.rank, self.world = _rank_world(rank, world)
         self.seq = 0
+        self.width = codec.COLS + getattr(codec, "n_dc", 0)
+        self.host_tag = 0  # the last gather's summed host-key counts (the same on every rank)
 
     def _stamp(self, r: np.ndarray) -> np.ndarray:
         r[:, 0] = self.rank
@@ -659,55 +680,47 @@ class _Replica:
         self.seq += r.shape[0]
         return r
 
-    def originate(self, batch) -> np.ndarray:
+    def _message(self, rows: np.ndarray, failed: bool = False):
+        hk = getattr(self.codec, "host_keys", None)
+        new = len(hk - self.codec.reported) if hk is not None else 0
+        return rows, min(new, _MSG_FAIL - 1) | (_MSG_FAIL if failed else 0)
+
+    def failed_message(self):
+        return self._message(np.zeros((0, self.width), np.int64), failed=True)
+
+    def originate(self, batch):
         """Apply this replica's own effects (CSR batch over all keys, stream
         order per key); returns them plus the extras they produced, as the
         rows this replica sends."""
         own = self._stamp(self.codec.rows_of_batch(batch))
         ex = self.codec.apply(self.engine, own) if own.shape[0] else own[:0]
-        return np.concatenate([own, self._stamp(ex)])
+        return self._message(np.concatenate([own, self._stamp(ex)]))
 
-    def deliver(self, gathered: np.ndarray) -> np.ndarray:
+    def read(self, parts):
+        self.host_tag = sum(t & (_MSG_FAIL - 1) for _, t in parts)
+        rows = np.concatenate([p for p, _ in parts])
+        return [o for o, (_, t) in enumerate(parts) if t & _MSG_FAIL], rows if rows.shape[0] else None
+
+    def deliver(self, gathered: np.ndarray):
         """Apply every other origin's rows in canonical order; returns the
         extras that produced, stamped as this replica's effects."""
         r = canonical(gathered[gathered[:, 0] != self.rank])
-        if not r.shape[0]:
-            return r
-        return self._stamp(self.codec.apply(self.engine, r))
+        return self._message(self._stamp(self.codec.apply(self.engine, r)) if r.shape[0] else r)
 
     def step(self, batch, max_rounds: int = 64) -> int:
-        """One replication step over torch.distributed (all_gather_rows);
-        returns the number of delivery rounds.  A topk_rmv replica whose engine
-        handed keys to the host path (CCRDT_EKEYCAP) raises KeyCapacityError
-        on every rank once the step has quiesced (raise_host_keys)."""
-        out = self.originate(batch)
-        for rounds in range(max_rounds):
-            allr, n_new = all_gather_rows(out, self.new_host_keys())
-            if not allr.shape[0]:
-                if n_new:  # (the same on every rank: the gathered sum)
-                    self.check_host_keys(rounds)
-                return rounds
-            out = self.deliver(allr)
-        raise RuntimeError("replication did not quiesce")
-
-    def new_host_keys(self) -> int:
-        """Keys this replica's codec handed to the host path and has not yet
-        reported."""
-        hk = getattr(self.codec, "host_keys", None)
-        return len(hk - self.codec.reported) if hk is not None else 0
-
-    def check_host_keys(self, result=None, local: bool = False) -> None:
-        """Collective (unless `local`: replicas held by one process): raise on
-        every rank when any rank's codec handed keys to the host path since
-        the last report."""
-        hk = getattr(self.codec, "host_keys", None)
-        if hk is None:
-            return
-        new = hk - self.codec.reported
-        dist = None if local else _dist()
-        coll = TorchCollective(dist) if dist is not None and self.world > 1 else None
-        self.codec.reported |= new
-        raise_host_keys(new, result, coll)
+        """One replication step over torch.distributed (all_gather_rows: the
+        sizes with the tag, then the padded rows); returns the number of
+        delivery rounds.  A topk_rmv replica whose engine handed keys to the
+        host path (CCRDT_EKEYCAP) raises KeyCapacityError on every rank once
+        the step has quiesced (raise_host_keys; its gather runs only when the
+        last round's summed tags say some rank has one).  A rank whose apply
+        raises makes every rank raise PeerStepError (_replicate)."""
+        coll = TorchCollective() if _dist() is not None and self.world > 1 else None
+        gather = (lambda m: all_gather_rows(*m, coll=coll)) if coll is not None else None
+        rounds = _replicate([self], [batch], gather, max_rounds)
+        if self.host_tag:
+            _report_host_keys([self], rounds, coll)
+        return rounds
 
     def export(self):
         return self.engine.export()
@@ -718,9 +731,6 @@ class ReplicatedTopkRmv(_Replica):
 
     def __init__(self, n_keys: int, k: int = 100, n_dc: int = 8, rank: int | None = None,
                  world: int | None = None, engine=None, device: int = 0):
-        dist = _dist()
-        rank = rank if rank is not None else (dist.get_rank() if dist else 0)
-        world = world if world is not None else (dist.get_world_size() if dist else 1)
         if engine is None:
             from .engine import TopkRmvEngine
             engine = TopkRmvEngine(n_keys, k, n_dc, device=device)
@@ -732,9 +742,6 @@ class ReplicatedLeaderboard(_Replica):
 
     def __init__(self, n_keys: int, k: int = 100, rank: int | None = None,
                  world: int | None = None, engine=None, device: int = 0):
-        dist = _dist()
-        rank = rank if rank is not None else (dist.get_rank() if dist else 0)
-        world = world if world is not None else (dist.get_world_size() if dist else 1)
         if engine is None:
             from .types import LeaderboardEngine
             engine = LeaderboardEngine(n_keys, k, device=device)
@@ -743,21 +750,11 @@ class ReplicatedLeaderboard(_Replica):
 
 def replicate_local(replicas, batches, max_rounds: int = 64) -> int:
     """The replication step of `replicas` (one process, e.g. several engines
-    on one GPU), exchanging rows by concatenation instead of all_gather."""
-    outs = [r.originate(b) for r, b in zip(replicas, batches)]
-    for rounds in range(max_rounds):
-        allr = np.concatenate(outs)
-        if not allr.shape[0]:
-            new = set()
-            for r in replicas:  # (every replica's report, then one raise)
-                hk = getattr(r.codec, "host_keys", None)
-                if hk is not None:
-                    new |= hk - r.codec.reported
-                    r.codec.reported |= hk
-            raise_host_keys(new, rounds)
-            return rounds
-        outs = [r.deliver(allr) for r in replicas]
-    raise RuntimeError("replication did not quiesce")
+    on one GPU), exchanging rows by concatenation instead of all_gather;
+    every replica's host-path keys are reported by one raise."""
+    rounds = _replicate(replicas, batches, None, max_rounds)
+    _report_host_keys(replicas, rounds)
+    return rounds
 
 
 # ------------------------------------------- key-sharded word histogram
@@ -790,20 +787,12 @@ def _gather_bytes(wb: np.ndarray, starts: np.ndarray, lens: np.ndarray) -> np.nd
 def all_to_all_v(send: np.ndarray, splits: list[int]) -> tuple[np.ndarray, list[int]]:
     """Variable all-to-all of a 1-D array (RCCL all_to_all_single on the GPU
     node, gloo on the host): rank r receives the slice `splits[r]` of every
-    rank's `send`, concatenated in rank order.  Returns (received, sizes)."""
-    import torch
-    dist = _dist()
-    if dist is None:
+    rank's `send`, concatenated in rank order.  Returns (received, sizes).
+    TorchCollective.all_to_all_v of the global process group on a host array."""
+    if _dist() is None:
         return send, splits
-    dev = _device_for(dist)
-    world = dist.get_world_size()
-    sz = torch.tensor(splits, dtype=torch.int64, device=dev)
-    rsz = torch.empty(world, dtype=torch.int64, device=dev)
-    dist.all_to_all_single(rsz, sz)
-    rsplits = [int(v) for v in rsz.cpu()]
-    t = torch.from_numpy(np.ascontiguousarray(send)).to(dev)
-    out = torch.empty(sum(rsplits), dtype=t.dtype, device=dev)
-    dist.all_to_all_single(out, t, rsplits, list(splits))
+    coll = TorchCollective()
+    out, rsplits = coll.all_to_all_v(_wire_in(coll, send), splits)
     return out.cpu().numpy(), rsplits
 
 
@@ -820,9 +809,7 @@ class ShardedWordcount:
 
     def __init__(self, n_keys: int = 1, wdc: bool = False, rank: int | None = None,
                  world: int | None = None, local_factory=None, owned=None, device: int = 0):
-        dist = _dist()
-        self.rank = rank if rank is not None else (dist.get_rank() if dist else 0)
-        self.world = world if world is not None else (dist.get_world_size() if dist else 1)
+        self.rank, self.world = _rank_world(rank, world)
         self.n_keys = n_keys
         from .types import WordcountEngine, WordDocumentCountEngine
         E = WordDocumentCountEngine if wdc else WordcountEngine
@@ -926,19 +913,26 @@ class TorchCollective:
             return out
         return torch.stack(self.all_gather(t))
 
-    def all_gather_v(self, t):
-        """Rank r's t (variable first dimension) -> [t of rank 0, ..., t of rank W-1]."""
+    def all_gather_v(self, t, tag=None):
+        """Rank r's t (variable first dimension) -> [t of rank 0, ..., t of rank
+        W-1]: the sizes' gather, then one padded gather.  `tag`: a word of this
+        rank's that rides the sizes' gather; then returns (parts, every rank's
+        tag), and leaves the padded gather out when no rank has anything."""
         import torch
         w = self._wire(t)
-        n = torch.tensor([w.shape[0]], dtype=torch.int64, device=w.device)
+        n = torch.tensor([w.shape[0], 0 if tag is None else int(tag)], dtype=torch.int64, device=w.device)
         ns = [torch.zeros_like(n) for _ in range(self.world)]
         self.dist.all_gather(ns, n)
-        counts = [int(c) for c in torch.cat(ns).cpu()]
+        hv = torch.stack(ns).cpu().tolist()
+        counts, tags = [h[0] for h in hv], [h[1] for h in hv]
+        if tag is not None and not sum(counts):
+            return [t[:0]] * self.world, tags
         buf = torch.zeros((max(max(counts), 1),) + tuple(w.shape[1:]), dtype=w.dtype, device=w.device)
         buf[:w.shape[0]] = w
         outs = [torch.empty_like(buf) for _ in range(self.world)]
         self.dist.all_gather(outs, buf)
-        return [o[:c].to(t.device) for o, c in zip(outs, counts)]
+        parts = [o[:c].to(t.device) for o, c in zip(outs, counts)]
+        return parts if tag is None else (parts, tags)
 
     def all_to_all_v(self, t, splits):
         """Rank r sends t[sum(splits[:d]) : sum(splits[:d+1])] to rank d;
@@ -1072,43 +1066,86 @@ def _lb_apply_csr_device(engine, kp, kind, id_, score):
             e[:, 3].contiguous())
 
 
-# A replica's message for one delivery round is one flat int64 tensor of RUNS,
-# each run sorted by key and holding rows of one origin in seq order: a
-# replica's first message is its batch (seq 0..n-1) and then the batch's
-# extras (seq n..), later messages one run of extras.  Layout:
-# [n_runs, len_0, len_1 | run 0: key[len_0] kind[len_0] id[len_0] score[len_0] | run 1 ...]
-# (an empty message is a zero-length tensor).  The canonical order of
-# ReplicatedLeaderboard (key, origin, seq) is then a merge of the runs, each
-# row's position counted by binary search in the other runs: no sort and no
+# A device replica's message for one delivery round is one flat int64 tensor of
+# RUNS, each run sorted by key and holding effects of one origin in seq order:
+# a replica's first message is its batch (seq 0..n-1) and then the batch's
+# extras (seq n..), later messages one run of extras.  Layout: a header of
+# _MSG_HDR words [n_runs | failed << 32, then each run's counts: its length,
+# and for topk_rmv its clock rows and rmv ops], then per run its columns
+# (length words each) and, for topk_rmv, its clock rows (rows x n_dc words).
+# An empty message is a zero-length tensor, a failed one a header alone.  The
+# canonical (key, origin, seq) order of the host protocol is then a merge of
+# the gathered runs taken in (origin, message position) order: no sort and no
 # gather of rows (the [n, 6] rows of the host protocol cost 3x the step).
-_LB_HDR = 3
+_MSG_HDR = 8  # word 0 and two runs of three counts, zero-padded
 
 
-def _lb_message(runs, device=None):
-    import torch
-    runs = [r for r in runs if r is not None and int(r[0].shape[0])]
-    if not runs:
-        return torch.empty(0, dtype=torch.int64, device=device if device is not None else "cuda")
-    dev = runs[0][0].device
-    lens = [int(r[0].shape[0]) for r in runs]
-    hdr = torch.tensor([len(runs)] + lens + [0] * (_LB_HDR - 1 - len(runs)), dtype=torch.int64, device=dev)
-    return torch.cat([hdr] + [c.to(torch.int64) for r in runs for c in r])
+@dataclass(frozen=True)
+class _RunCodec:
+    """The message format of one flavour.  A run is (counts, columns, block):
+    `counts` its n_counts header words, the first the length of each column,
+    the second the rows of the trailing block (row_words words each; none
+    when 0); `cols` the dtype name ("int64", "uint8") each column comes back as."""
+    cols: tuple
+    n_counts: int = 1
+    row_words: int = 0
+
+    def pack(self, runs, device, failed: bool = False):
+        """The message of `runs` (None and zero-length ones left out)."""
+        import torch
+        runs = [r for r in runs if r is not None and r[0][0]]
+        if not runs and not failed:
+            return torch.empty(0, dtype=torch.int64, device=device)
+        hdr = [len(runs) | (_MSG_FAIL if failed else 0)] + [int(c) for r in runs for c in r[0]]
+        hdr += [0] * (_MSG_HDR - len(hdr))
+        body = [t.to(torch.int64) for _, cols, block in runs for t in (*cols, *([block] if self.row_words else []))]
+        return torch.cat([torch.tensor(hdr, dtype=torch.int64, device=device)] + body)
+
+    @staticmethod
+    def headers(msgs):
+        """Each message's header as a list of ints (None for an empty
+        message), and the origins whose header says failed: one host read."""
+        import torch
+        full = [m for m in msgs if int(m.shape[0])]
+        hv = iter(torch.stack([m[:_MSG_HDR] for m in full]).cpu().tolist() if full else [])
+        hdrs = [next(hv) if int(m.shape[0]) else None for m in msgs]
+        return hdrs, [o for o, h in enumerate(hdrs) if h is not None and h[0] & _MSG_FAIL]
+
+    def unpack(self, msg, hdr):
+        """The runs of one message, over slices of it."""
+        import torch
+        off, runs = _MSG_HDR, []
+        for j in range(hdr[0] & (_MSG_FAIL - 1)):
+            counts = hdr[1 + self.n_counts * j:1 + self.n_counts * (j + 1)]
+            cols = []
+            for dt in self.cols:
+                cols.append(msg[off:off + counts[0]].to(getattr(torch, dt)))
+                off += counts[0]
+            block = msg[off:off + counts[1] * self.row_words] if self.row_words else None
+            off += counts[1] * self.row_words if self.row_words else 0
+            runs.append((counts, cols, block))
+        return runs
 
 
-def _lb_runs(msgs):
-    """The runs of several messages, in message order (one header read)."""
-    import torch
-    msgs = [m for m in msgs if int(m.shape[0])]
-    if not msgs:
-        return []
-    hdrs = torch.stack([m[:_LB_HDR] for m in msgs]).cpu().tolist()
-    runs = []
-    for m, h in zip(msgs, hdrs):
-        off = _LB_HDR
-        for L in h[1:1 + h[0]]:
-            runs.append(tuple(m[off + j * L:off + (j + 1) * L] for j in range(4)))
-            off += 4 * L
-    return runs
+_LB_MSG = _RunCodec(("int64",) * 4)  # the leaderboard message: columns key, kind, id, score
+
+
+class _DeviceReplica:
+    """What the two device replicas share: the round of a gather and the
+    failed message.  A subclass sets .engine, .rank, .world, .dev and .msg
+    (its _RunCodec) and has originate() and deliver()."""
+
+    def read(self, parts):
+        hdrs, failed = self.msg.headers(parts)
+        return failed, None if all(h is None for h in hdrs) else (parts, hdrs)
+
+    def failed_message(self):
+        return self.msg.pack([], self.dev, failed=True)
+
+    def _runs(self, rnd):
+        """The runs of every other origin's message of a round, in origin order."""
+        return [r for o, (p, h) in enumerate(zip(*rnd)) if o != self.rank and h is not None
+                for r in self.msg.unpack(p.to(self.dev), h)]
 
 
 def _lb_merge_runs(runs, n_keys: int):
@@ -1138,19 +1175,27 @@ def _lb_merge_runs(runs, n_keys: int):
     return kp, kind_o, id_o, sc_o
 
 
-class LbDeviceReplica:
+def _lb_run(cols):
+    """A (key, kind, id, score) run, or None, as the codec takes it."""
+    return None if cols is None else ((int(cols[0].shape[0]),), cols, None)
+
+
+class LbDeviceReplica(_DeviceReplica):
     """One DC replica of n_keys leaderboards with its effect rows on the
     device (BASELINE configs[3]; the protocol of ReplicatedLeaderboard,
     leaderboard.erl:128-134,282-284, whose canonical (key, origin, seq) order
-    the run merge reproduces).  A step is originate() and then deliver() per
-    round, each returning the message (runs, above) this replica sends; the
-    exchange between them is injected: lb_replicate_step with a
+    the run merge reproduces).  A step (_replicate) is originate() and then
+    deliver() per round, each returning the message (runs, above) this replica
+    sends; the exchange between them is injected: lb_replicate_step with a
     TorchCollective (one process per GPU) or lb_replicate_device_local
     (replicas held by one process, exchange = the list of every replica's
-    messages).  Both run exactly these two methods."""
+    messages)."""
 
     def __init__(self, engine, rank: int, world: int):
+        import torch
         self.engine, self.rank, self.world = engine, rank, world
+        self.dev = torch.device("cuda", engine.device)
+        self.msg = _LB_MSG
 
     def originate(self, batch):
         """Apply this replica's own batch (device (key_ptr, kind, id, score),
@@ -1163,30 +1208,25 @@ class LbDeviceReplica:
         dev = kind.device
         ex = _lb_apply_csr_device(self.engine, kp, kind.contiguous(), id_.contiguous(), score.contiguous())
         keys = torch.repeat_interleave(torch.arange(nk, device=dev), kp[1:] - kp[:-1], output_size=n)
-        return _lb_message([(keys, kind, id_, score), ex])
+        return self.msg.pack([_lb_run((keys, kind, id_, score)), _lb_run(ex)], self.dev)
 
-    def deliver(self, parts):
-        """Apply the messages of every other origin (parts[o] = origin o's)
+    def deliver(self, rnd):
+        """Apply the messages of every other origin (a round of read())
         merged into canonical order; returns the message of the extras that
         produced."""
-        runs = _lb_runs([p for o, p in enumerate(parts) if o != self.rank])
+        runs = [tuple(cols) for _, cols, _ in self._runs(rnd)]
         if not runs:
-            return _lb_message([], parts[self.rank].device if len(parts) > self.rank else None)
+            return self.msg.pack([], self.dev)
         kp, kind, id_, sc = _lb_merge_runs(runs, self.engine.n_keys)
-        return _lb_message([_lb_apply_csr_device(self.engine, kp, kind, id_, sc)])
+        return self.msg.pack([_lb_run(_lb_apply_csr_device(self.engine, kp, kind, id_, sc))], self.dev)
 
 
 def lb_replicate_step(replica: LbDeviceReplica, batch, coll, max_rounds: int = 64) -> int:
     """One replication step of this rank's replica over a collective
     (TorchCollective: RCCL over xGMI, or gloo staged through the host);
-    returns the number of delivery rounds."""
-    out = replica.originate(batch)
-    for rounds in range(max_rounds):
-        parts = coll.all_gather_v(out)
-        if not any(int(p.shape[0]) for p in parts):
-            return rounds
-        out = replica.deliver(parts)
-    raise RuntimeError("replication did not quiesce")
+    returns the number of delivery rounds.  A rank whose apply raises makes
+    every rank raise PeerStepError (_replicate)."""
+    return _replicate([replica], [batch], coll.all_gather_v, max_rounds)
 
 
 def lb_replicate_device_local(engines, batches, max_rounds: int = 64) -> int:
@@ -1194,32 +1234,16 @@ def lb_replicate_device_local(engines, batches, max_rounds: int = 64) -> int:
     all-gather is the list of every replica's messages).  `batches` are
     (key_ptr, kind, id, score) device tensors, CSR by key.  Returns the
     number of delivery rounds."""
-    reps = [LbDeviceReplica(e, r, len(engines)) for r, e in enumerate(engines)]
-    outs = [r.originate(b) for r, b in zip(reps, batches)]
-    for rounds in range(max_rounds):
-        if not any(int(o.shape[0]) for o in outs):
-            return rounds
-        outs = [r.deliver(outs) for r in reps]
-    raise RuntimeError("replication did not quiesce")
+    return _replicate([LbDeviceReplica(e, r, len(engines)) for r, e in enumerate(engines)], batches, None, max_rounds)
 
 
 # ------------------------- topk_rmv replication mode, on the device
-# The protocol of ReplicatedTopkRmv with every effect kept in HBM.  A replica's
-# message for one delivery round is one flat int64 tensor of RUNS
-# (ccrdt_trmv_run: effects of one origin in seq order, sorted by key): its
-# first message is its batch and then the batch's extras, later messages one
-# run of extras.  Layout: a header of _TRMV_HDR words
-# [n_runs | failed << 32, then per run: ops, clock rows, rmv ops], then per run
-# the columns key, kind, id, score, dc, ts (n words each) and its clock rows
-# (rows x n_dc words); an empty message is a zero-length tensor.  The canonical
-# (key, origin, seq) order of the host protocol is the merge of the gathered
-# runs taken in (origin, message position) order, done by
-# ccrdt_trmv_merge_runs_device; the extras come back as a run in stream order
-# from ccrdt_trmv_extras_run_device.  torch only packs and unpacks columns.
-_TRMV_HDR = 8
-_TRMV_FAIL = 1 << 32
-
-
+# The protocol of ReplicatedTopkRmv with every effect kept in HBM.  A run is a
+# ccrdt_trmv_run: the columns key, kind, id, score, dc, ts and its own clock
+# rows, with the counts ops, clock rows, rmv ops in the header.  The merge of
+# the gathered runs is done by ccrdt_trmv_merge_runs_device; the extras come
+# back as a run in stream order from ccrdt_trmv_extras_run_device.  torch only
+# packs and unpacks columns.
 class _TensorBuf:
     """A torch tensor as a device buffer of the engine API (`.p`, `.close()`)."""
 
@@ -1249,72 +1273,45 @@ def _dev_tensor(buf, dtype, n: int, device):
     return torch.as_tensor(_Cai(), device=device)
 
 
-def _trmv_message(runs, n_dc: int, device, failed: bool = False):
-    """The message of DeviceTrmvRuns (None and empty ones left out)."""
+def _trmv_run(r, n_dc: int, device):
+    """A DeviceTrmvRun, or None, as the codec takes it (no copy)."""
     import torch
 
     from .engine import DeviceTrmvRun
-    runs = [r for r in runs if r is not None and r.n_ops]
-    if not runs and not failed:
-        return torch.empty(0, dtype=torch.int64, device=device)
-    hdr = [len(runs) | (_TRMV_FAIL if failed else 0)]
-    parts = []
-    for r in runs:
-        hdr += [r.n_ops, r.n_rmv, r.n_ops if r.n_rmv_ops is None else r.n_rmv_ops]
-        for c, dt in zip(DeviceTrmvRun.COLUMNS[:-1], DeviceTrmvRun.DTYPES):
-            parts.append(_dev_tensor(r.bufs[c], torch.uint8 if dt == np.uint8 else torch.int64, r.n_ops,
-                                     device).to(torch.int64))
-        parts.append(_dev_tensor(r.bufs["rmv_vc"], torch.int64, r.n_rmv * n_dc, device))
-    hdr += [0] * (_TRMV_HDR - len(hdr))
-    return torch.cat([torch.tensor(hdr, dtype=torch.int64, device=device)] + parts)
+    if r is None:
+        return None
+    cols = [_dev_tensor(r.bufs[c], torch.uint8 if dt == np.uint8 else torch.int64, r.n_ops, device)
+            for c, dt in zip(DeviceTrmvRun.COLUMNS[:-1], DeviceTrmvRun.DTYPES)]
+    return ((r.n_ops, r.n_rmv, r.n_ops if r.n_rmv_ops is None else r.n_rmv_ops), cols,
+            _dev_tensor(r.bufs["rmv_vc"], torch.int64, r.n_rmv * n_dc, device))
 
 
-def _trmv_headers(msgs):
-    """Each message's header as a list of ints (None for an empty message): one host read."""
-    import torch
-    full = [m for m in msgs if int(m.shape[0])]
-    hv = iter(torch.stack([m[:_TRMV_HDR] for m in full]).cpu().tolist() if full else [])
-    return [next(hv) if int(m.shape[0]) else None for m in msgs]
-
-
-def _trmv_unpack(msg, hdr, n_dc: int):
-    """The runs of one message, as DeviceTrmvRuns over slices of it."""
-    import torch
-
+def _trmv_msg(n_dc: int) -> _RunCodec:
+    """The topk_rmv message of n_dc-wide clocks."""
     from .engine import DeviceTrmvRun
-    off, runs = _TRMV_HDR, []
-    for j in range(hdr[0] & 0xFFFFFFFF):
-        n, rows, n_rmv_ops = hdr[1 + 3 * j:4 + 3 * j]
-        cols = {}
-        for c, dt in zip(DeviceTrmvRun.COLUMNS[:-1], DeviceTrmvRun.DTYPES):
-            t = msg[off:off + n]
-            cols[c] = _TensorBuf(t.to(torch.uint8) if dt == np.uint8 else t)
-            off += n
-        cols["rmv_vc"] = _TensorBuf(msg[off:off + rows * n_dc])
-        off += rows * n_dc
-        runs.append(DeviceTrmvRun.from_buffers(n, rows, cols, n_rmv_ops))
-    return runs
+    return _RunCodec(tuple(np.dtype(dt).name for dt in DeviceTrmvRun.DTYPES[:-1]), 3, n_dc)
 
 
-class TrmvDeviceReplica:
+class TrmvDeviceReplica(_DeviceReplica):
     """One DC replica of an n_keys topk_rmv keyspace with its effects on the
     device (BASELINE configs[3]): the protocol of ReplicatedTopkRmv
     (topk_rmv.erl:140-148; extras :236-237, :294-295), whose canonical (key,
-    origin, seq) order the run merge reproduces.  A step is originate() and
-    then deliver() per round, each returning the message (above) this replica
-    sends; the exchange between them is injected: trmv_replicate_step with a
-    TorchCollective (one process per GPU) or trmv_replicate_device_local
-    (replicas held by one process).  Both run exactly these two methods.
+    origin, seq) order the run merge reproduces.  A step (_replicate) is
+    originate() and then deliver() per round, each returning the message
+    (above) this replica sends; the exchange between them is injected:
+    trmv_replicate_step with a TorchCollective (one process per GPU) or
+    trmv_replicate_device_local (replicas held by one process).
     The host reads of a delivery are the gathered headers, the status records
     of the merge and of the extras run, and apply_device's own.  A key over
     the engine's per-key capacity makes apply_device raise KeyCapacityError
-    (the batch committed for every other key); the drivers say what happens
+    (the batch committed for every other key); _replicate says what happens
     then.  Continuing such keys on the host path stays with ReplicatedTopkRmv."""
 
     def __init__(self, engine, rank: int, world: int):
         import torch
         self.engine, self.rank, self.world = engine, rank, world
         self.dev = torch.device("cuda", engine.device)
+        self.msg = _trmv_msg(engine.n_dc)
 
     def _alloc(self, nbytes: int):
         import torch
@@ -1327,6 +1324,9 @@ class TrmvDeviceReplica:
         _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.dev))
         self.engine.apply_device(db)
         return self.engine.extras_run_device(db.n_ops, db.n_ops - (db.n_rmv_ops or 0), alloc=self._alloc)
+
+    def _message(self, runs):
+        return self.msg.pack([_trmv_run(r, self.engine.n_dc, self.dev) for r in runs], self.dev)
 
     def originate(self, batch):
         """Apply this replica's own DeviceTrmvBatch (CSR by key, stream order:
@@ -1341,47 +1341,32 @@ class TrmvDeviceReplica:
         key = torch.repeat_interleave(torch.arange(nk, device=self.dev), kp[1:] - kp[:-1], output_size=n)
         own = DeviceTrmvRun.from_buffers(n, batch.n_rmv, {"key": _TensorBuf(key), **{
             c: batch.bufs[c] for c in DeviceTrmvRun.COLUMNS[1:]}}, batch.n_rmv_ops)
-        return _trmv_message([own, ex], self.engine.n_dc, self.dev)
+        return self._message([own, ex])
 
-    def deliver(self, parts, hdrs=None):
-        """Apply the messages of every other origin (parts[o] = origin o's;
-        hdrs = _trmv_headers(parts) where the caller has read them) merged
-        into canonical order; returns the message of the extras that produced."""
+    def deliver(self, rnd):
+        """Apply the messages of every other origin (a round of read())
+        merged into canonical order; returns the message of the extras that
+        produced."""
         import torch
-        hdrs = _trmv_headers(parts) if hdrs is None else hdrs
-        runs = [r for o, (p, h) in enumerate(zip(parts, hdrs)) if o != self.rank and h is not None
-                for r in _trmv_unpack(p.to(self.dev), h, self.engine.n_dc)]
+
+        from .engine import DeviceTrmvRun
+        runs = [DeviceTrmvRun.from_buffers(n, rows, {c: _TensorBuf(t) for c, t in zip(DeviceTrmvRun.COLUMNS,
+                                                                                      (*cols, block))}, n_rmv_ops)
+                for (n, rows, n_rmv_ops), cols, block in self._runs(rnd)]
         if not runs:
-            return _trmv_message([], self.engine.n_dc, self.dev)
+            return self._message([])
         _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.dev))
         merged = self.engine.merge_runs_device(runs, alloc=self._alloc)
-        return _trmv_message([self._apply(merged)], self.engine.n_dc, self.dev)
+        return self._message([self._apply(merged)])
 
 
 def trmv_replicate_step(replica: TrmvDeviceReplica, batch, coll, max_rounds: int = 64) -> int:
     """One replication step of this rank's replica over a collective
     (TorchCollective: RCCL over xGMI, or gloo staged through the host);
     returns the number of delivery rounds.  A rank whose apply raises (a key
-    over the per-key capacity, an invalid op, a device error) sends a message
-    whose header carries the failure word, still takes part in the gather, and
-    then every rank raises PeerStepError (the failed rank's own exception
-    chained), so no rank is left in a collective."""
-    def guarded(fn, *args):
-        try:
-            return fn(*args), None
-        except Exception as e:  # noqa: BLE001 - re-raised on every rank after the gather
-            return _trmv_message([], replica.engine.n_dc, replica.dev, failed=True), e
-    out, err = guarded(replica.originate, batch)
-    for rounds in range(max_rounds):
-        parts = coll.all_gather_v(out)
-        hdrs = _trmv_headers(parts)
-        failed = [r for r, h in enumerate(hdrs) if h is not None and h[0] & _TRMV_FAIL]
-        if failed:
-            raise PeerStepError(failed) from err
-        if all(h is None for h in hdrs):
-            return rounds
-        out, err = guarded(replica.deliver, parts, hdrs)
-    raise RuntimeError("replication did not quiesce")
+    over the per-key capacity, an invalid op, a device error) makes every rank
+    raise PeerStepError (_replicate)."""
+    return _replicate([replica], [batch], coll.all_gather_v, max_rounds)
 
 
 def trmv_replicate_device_local(engines, batches, max_rounds: int = 64) -> int:
@@ -1390,24 +1375,4 @@ def trmv_replicate_device_local(engines, batches, max_rounds: int = 64) -> int:
     DeviceTrmvBatches, CSR by key.  Returns the number of delivery rounds.  A
     KeyCapacityError of a replica's apply_device propagates once every replica
     has applied the round."""
-    from ._lib import KeyCapacityError
-    reps = [TrmvDeviceReplica(e, r, len(engines)) for r, e in enumerate(engines)]
-
-    def round_of(calls):
-        outs, first = [], None
-        for r, (fn, args) in zip(reps, calls):
-            try:
-                outs.append(fn(*args))
-            except KeyCapacityError as e:
-                first = first or e
-                outs.append(_trmv_message([], r.engine.n_dc, r.dev))
-        if first is not None:
-            raise first
-        return outs
-    outs = round_of([(r.originate, (b,)) for r, b in zip(reps, batches)])
-    for rounds in range(max_rounds):
-        hdrs = _trmv_headers(outs)
-        if all(h is None for h in hdrs):
-            return rounds
-        outs = round_of([(r.deliver, (outs, hdrs)) for r in reps])
-    raise RuntimeError("replication did not quiesce")
+    return _replicate([TrmvDeviceReplica(e, r, len(engines)) for r, e in enumerate(engines)], batches, None, max_rounds)

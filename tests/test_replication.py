@@ -26,6 +26,7 @@ from antidote_ccrdt_amd.cluster import (ReplicatedLeaderboard, ReplicatedTopkRmv
                                         exchange_local, replicate_local, word_owner)
 from antidote_ccrdt_amd.engine import gen_trmv
 from antidote_ccrdt_amd.types import LbState, _csr
+from replication_helpers import ThreadCollective
 
 NK, K, D, STEPS = 300, 3, 8, 3
 
@@ -343,44 +344,6 @@ def test_wc_partition_device_row_limit(gpu, monkeypatch):
 
 
 # ------------------------------------------------ injected collectives
-class ThreadCollective:
-    """In-process stand-in for TorchCollective: W threads, one per rank,
-    meet at a barrier and read each other's tensors (the exchange by
-    slicing), so the per-rank drivers run unchanged."""
-
-    def __init__(self, world):
-        import threading
-        self.world = world
-        self.bar = threading.Barrier(world)
-        self.box = [None] * world
-
-    def view(self, rank):
-        coll = self
-
-        class _V:
-            world = coll.world
-
-            def all_gather_v(self, t):
-                coll.box[rank] = t
-                coll.bar.wait()
-                out = list(coll.box)
-                coll.bar.wait()
-                return out
-
-            def all_to_all_v(self, t, splits):
-                import torch
-                coll.box[rank] = (t, [int(x) for x in splits])
-                coll.bar.wait()
-                parts, sizes = [], []
-                for src, sp in coll.box:
-                    o = sum(sp[:rank])
-                    parts.append(src[o:o + sp[rank]])
-                    sizes.append(sp[rank])
-                coll.bar.wait()
-                return torch.cat(parts), sizes
-        return _V()
-
-
 def _coll_worker(rank, world, port, errf):
     """TorchCollective over gloo (CPU tensors): variable all-gather and
     all-to-all."""
@@ -538,10 +501,10 @@ def test_lb_run_merge_is_canonical(n_runs):
     merged by binary-search rank equal a stable sort by (key, run, index) --
     the canonical (key, origin, seq) order of ReplicatedLeaderboard -- with
     many equal keys across and inside runs, empty keys and empty runs; and the
-    messages round-trip through _lb_message / _lb_runs."""
+    messages round-trip through the leaderboard run codec (_LB_MSG)."""
     import torch
 
-    from antidote_ccrdt_amd.cluster import _lb_merge_runs, _lb_message, _lb_runs
+    from antidote_ccrdt_amd.cluster import _LB_MSG, _lb_merge_runs, _lb_run
     rng = np.random.default_rng(n_runs)
     nk = 40
     runs = []
@@ -551,8 +514,10 @@ def test_lb_run_merge_is_canonical(n_runs):
         cols = (key, rng.integers(0, 3, n).astype(np.int64), rng.integers(0, 10**6, n).astype(np.int64),
                 np.arange(n, dtype=np.int64) + 1000 * r)  # score: (run, index) tag
         runs.append(tuple(torch.from_numpy(c) for c in cols))
-    msgs = [_lb_message(runs[i:i + 2]) for i in range(0, n_runs, 2)]
-    back = _lb_runs(msgs)
+    msgs = [_LB_MSG.pack([_lb_run(r) for r in runs[i:i + 2]], "cpu") for i in range(0, n_runs, 2)]
+    hdrs, failed = _LB_MSG.headers(msgs)
+    assert not failed
+    back = [tuple(cols) for m, h in zip(msgs, hdrs) for _, cols, _ in _LB_MSG.unpack(m, h)]
     nonempty = [r for r in runs if r[0].shape[0]]
     assert len(back) == len(nonempty)
     for a, b in zip(back, nonempty):
