@@ -33,7 +33,7 @@ INT = C.c_int
 
 class CcrdtError(RuntimeError):
     """A CCRDT_* return code other than OK (`code`).  Raised by
-    TopkRmvEngine.compact_device, merge_runs_device or extras_run_device, it carries `totals` = (ops, clock rows) of
+    TopkRmvEngine.compact_device, merge_runs_device, extras_run_device or downstream_device, it carries `totals` = (ops, clock rows) of
     the compacted batch as far as the call got to set them: with ENOMEM the
     true totals, to size the outputs by."""
     totals = None
@@ -84,6 +84,11 @@ class TrmvState(C.Structure):
                 ("obs_dc", P), ("m_ptr", P), ("m_id", P), ("m_score", P), ("m_ts", P),
                 ("m_dc", P), ("r_ptr", P), ("r_id", P), ("r_vc", P), ("min_valid", P),
                 ("min_id", P), ("min_score", P), ("min_ts", P), ("min_dc", P)]
+
+
+class Requests(C.Structure):
+    """ccrdtx_requests (include/ccrdt_ext.h)."""
+    _fields_ = [("n_req", I64), ("key_ptr", P), ("op", P), ("id", P), ("score", P), ("dc", P), ("ts", P)]
 
 
 class AvgOps(C.Structure):
@@ -222,6 +227,13 @@ SIGNATURES = {
                              P, P, P, P, P, P, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/ccrdt_ext.h (the
+# entry points added since the `ccrdt_` list above was frozen)
+EXT_SIGNATURES = {
+    "ccrdtx_trmv_downstream_device": (INT, [P, C.POINTER(Requests), C.POINTER(TrmvOps), I64, I64, P]),
+    "ccrdtx_lb_downstream_device": (INT, [P, C.POINTER(Requests), C.POINTER(LbOps), I64, P]),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -229,7 +241,7 @@ def _load():
             f"libccrdt.so not built at {LIB_PATH}: run `python -c 'import __graft_entry__ as g; "
             f"g.build()'` (hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:

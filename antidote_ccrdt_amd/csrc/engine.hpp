@@ -123,6 +123,9 @@ struct ccrdt_engine {
   // device log compaction (compact_kernels.hip; both types it serves): per-key
   // kept counts, each key's first clock row
   ccrdt::DevBuf cmp_cnt, cmp_rows;
+  // device downstream/2 (downstream_kernels.hip; it shares the compaction's
+  // scratch): each request's kind, where the caller does not take them
+  ccrdt::DevBuf dwn_kind;
   // replication mode (replicate_kernels.hip; it shares the compaction's
   // scratch): by output position the op's source and key; the extras run's
   // per-key output offsets

@@ -10,12 +10,6 @@
 
 namespace ccrdt {
 
-// Strict cmp/2 of topk_rmv (:389-395): (Score, Id, Ts), DcId ignored.
-__device__ __forceinline__ bool trmv_cmp(int64_t s1, int64_t i1, int64_t t1, int64_t s2, int64_t i2,
-                                         int64_t t2) {
-  return s1 > s2 || (s1 == s2 && i1 > i2) || (s1 == s2 && i1 == i2 && t1 > t2);
-}
-
 // ------------------------------------------------------------- capacity scan
 // New segment capacities per key: old counts + this batch's ops on the key.
 // Three exclusive scans (players, pool, rows) over n_keys, block = 256 x 4.

@@ -222,6 +222,12 @@ __device__ __forceinline__ bool gb_gt(int64_t s1, uint32_t d1, int64_t t1, int64
   return s1 > s2 || (s1 == s2 && (d1 > d2 || (d1 == d2 && t1 > t2)));
 }
 
+// Strict cmp/2 of topk_rmv (:389-395): (Score, Id, Ts), DcId ignored.
+__device__ __forceinline__ bool trmv_cmp(int64_t s1, int64_t i1, int64_t t1, int64_t s2, int64_t i2,
+                                         int64_t t2) {
+  return s1 > s2 || (s1 == s2 && i1 > i2) || (s1 == s2 && i1 == i2 && t1 > t2);
+}
+
 enum : uint32_t {
   TRMV_ERR_KIND = 1u,
   TRMV_ERR_DC = 2u,

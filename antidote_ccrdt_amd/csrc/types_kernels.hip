@@ -377,10 +377,7 @@ int launch_ovf_need(const uint32_t* list, uint64_t n, const uint64_t* key_ptr, c
 // disjoint by Id (Masked non-empty implies Observed full, so the not-full
 // insert of :252-258 never meets a Masked Id) — plus an LDS hash Id -> entry.
 // Min is an entry index; min/1 (:297-303) and get_largest/1 (:306-312) are
-// wave reductions over the entries.
-__device__ __forceinline__ bool lb_cmp(int64_t i1, int64_t s1, int64_t i2, int64_t s2) {
-  return s1 > s2 || (s1 == s2 && i1 > i2);  // cmp/2 (:289-294)
-}
+// wave reductions over the entries (lb_cmp, cmp/2: types_kernels.hpp).
 
 // ET = int32_t for NARROW boards (every Id and Score of the board fits 32
 // bits): 9 B per entry instead of 17, about twice the boards per CU.

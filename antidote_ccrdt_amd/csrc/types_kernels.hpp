@@ -119,6 +119,9 @@ struct LbArgs {
   int32_t seq;  // 1: sequential replay only (diagnostic, CCRDT_LB_SEQ=1)
 };
 enum : uint32_t { LB_ERR_KIND = 1u };
+__device__ __forceinline__ bool lb_cmp(int64_t i1, int64_t s1, int64_t i2, int64_t s2) {
+  return s1 > s2 || (s1 == s2 && i1 > i2);  // cmp/2 (leaderboard.erl:289-294)
+}
 
 struct LbDownArgs {
   int64_t n;

@@ -304,6 +304,37 @@ class DeviceTrmvRun(_DeviceTrmvColumns):
         return TrmvRun(*cols, self.bufs["rmv_vc"].to_host(np.int64, r * n_dc).reshape(r, n_dc))
 
 
+class DeviceRequests:
+    """downstream/2 requests resident in HBM (ccrdtx_requests), CSR by key,
+    request order inside a key: op 0 = {add, {Id, Score}}, 1 = {rmv, Id}
+    (leaderboard: {ban, Id}); dc and ts (an add's origin DC rank and clock)
+    are topk_rmv's and may be left out for a leaderboard."""
+    COLUMNS = ("key_ptr", "op", "id", "score", "dc", "ts")
+    DTYPES = (np.uint64, np.uint8, np.int64, np.int64, np.uint8, np.int64)
+
+    def __init__(self, key_ptr, op, id, score, dc=None, ts=None):
+        cols = dict(zip(self.COLUMNS, (key_ptr, op, id, score, dc, ts)))
+        self._set(len(cols["op"]), {n: DeviceArray(_c(cols[n], dt)) for n, dt in zip(self.COLUMNS, self.DTYPES)
+                                    if cols[n] is not None})
+
+    def _set(self, n_req: int, bufs: dict) -> None:
+        self.n_req, self.bufs = int(n_req), bufs
+        self.c = _lib.Requests(self.n_req, *[bufs[n].p if n in bufs else None for n in self.COLUMNS])
+
+    @classmethod
+    def from_buffers(cls, n_req: int, bufs: dict) -> "DeviceRequests":
+        """Requests over device buffers that already hold them: bufs maps the
+        names of COLUMNS (dc, ts: topk_rmv only) to buffers with a device
+        pointer `.p`, which the object owns from here on."""
+        d = cls.__new__(cls)
+        d._set(n_req, bufs)
+        return d
+
+    def close(self):
+        for d in self.bufs.values():
+            d.close()
+
+
 class _Engine:
     TYPE = -1
 
@@ -466,6 +497,29 @@ class TopkRmvEngine(_Engine):
         self._sized_call(lib.ccrdt_trmv_compact_device, "trmv_compact_device", co, bufs, C.byref(db.c), C.byref(co),
                          cap_ops, int(cap_rows))
         return DeviceTrmvBatch.from_buffers(co.n_ops, co.n_rmv_rows, bufs, n_rmv_ops=co.n_rmv_rows)
+
+    def downstream_device(self, req: DeviceRequests, cap_ops: int | None = None, cap_rows: int | None = None,
+                          want_kinds: bool = False):
+        """downstream/2 (topk_rmv.erl:102-124) of every request of a batch
+        resident in HBM, against the resident state as it is in stream order
+        (ccrdtx_trmv_downstream_device): the effect batch they make -- `noop`s
+        dropped, every rmv with a clock row of its key's replica Vc -- as a
+        device batch compact_device and apply_device take as it is.  Both
+        capacities default to the request count, which always suffices; a
+        result over either raises CcrdtError(ENOMEM) with `totals`.
+        want_kinds: also a DeviceArray uint8[n_req] of each request's kind
+        (_lib.NOOP: `noop`), what its client is answered with."""
+        cap_ops = req.n_req if cap_ops is None else int(cap_ops)
+        cap_rows = req.n_req if cap_rows is None else int(cap_rows)
+        bufs = self._op_bufs(DeviceTrmvBatch.COLUMNS, cap_ops, cap_rows, DeviceArray.empty)
+        if want_kinds:
+            bufs["req_kind"] = DeviceArray.empty(req.n_req)
+        co = _lib.TrmvOps(0, 0, *[bufs[n].p for n in DeviceTrmvBatch.COLUMNS])
+        self._sized_call(lib.ccrdtx_trmv_downstream_device, "trmv_downstream_device", co, bufs, C.byref(req.c),
+                         C.byref(co), cap_ops, cap_rows, bufs["req_kind"].p if want_kinds else None)
+        kinds = bufs.pop("req_kind", None)
+        batch = DeviceTrmvBatch.from_buffers(co.n_ops, co.n_rmv_rows, bufs, n_rmv_ops=co.n_rmv_rows)
+        return (batch, kinds) if want_kinds else batch
 
     def _sized_call(self, fn, where: str, co, bufs: dict, *args) -> None:
         """A device call that sets co.n_ops / co.n_rmv_rows: an error frees the

@@ -195,6 +195,32 @@ class LeaderboardEngine(_Engine):
         out.n = int(co.n_ops)
         return out
 
+    def downstream_device(self, req, cap_ops: int | None = None, want_kinds: bool = False):
+        """downstream/2 (leaderboard.erl:93-116) of every request of an
+        engine.DeviceRequests batch, against the resident boards as they are in
+        stream order (ccrdtx_lb_downstream_device): the effect batch they make
+        (`noop`s dropped; n = its op count) as a device batch compact_device
+        and apply_device take as it is.  cap_ops defaults to the request
+        count; a result over it raises CcrdtError(ENOMEM) with `totals`.
+        want_kinds: also a DeviceArray uint8[n_req] of each request's kind
+        (_lib.NOOP: `noop`)."""
+        from .engine import DeviceArray
+        cap_ops = req.n_req if cap_ops is None else int(cap_ops)
+        out = DeviceBatch.from_buffers(0, self._op_bufs(("key_ptr", "kind", "id", "score"), cap_ops, 0, DeviceArray.empty))
+        kinds = DeviceArray.empty(req.n_req) if want_kinds else None
+        co = _lib.LbOps(0, out["key_ptr"], out["kind"], out["id"], out["score"])
+        try:
+            check(lib.ccrdtx_lb_downstream_device(self.h, C.byref(req.c), C.byref(co), cap_ops,
+                                                  kinds.p if want_kinds else None), "lb_downstream_device")
+        except _lib.CcrdtError as err:
+            err.totals = (int(co.n_ops), 0)
+            out.close()
+            if kinds is not None:
+                kinds.close()
+            raise
+        out.n = int(co.n_ops)
+        return (out, kinds) if want_kinds else out
+
     def values(self, keys=None):
         """value/1 (leaderboard.erl:84-86) of `keys` (board indices in any
         order, repeats allowed; None: every board) read on the device: (ptr,
