@@ -24,6 +24,12 @@ TRMV_MAX_DC = 8
 # the run merge (ccrdt_trmv_merge_runs_device): runs per call, ops of one run per workgroup of its rank pass
 TRMV_MAX_RUNS = 32
 TRMV_MERGE_TILE = 256
+# the leaderboard's (ccrdtx_lb_merge_runs_device): runs per call, ops of one run per workgroup
+LB_MAX_RUNS = 32
+LB_MERGE_TILE = 256
+# the key column (ccrdtx_csr_keys_device): output positions per workgroup, keys of key_ptr it stages at a time
+CSR_KEYS_TILE = 1024
+CSR_KEYS_WIN = 1024
 
 P = C.c_void_p
 I64 = C.c_int64
@@ -101,6 +107,11 @@ class TopkOps(C.Structure):
 
 class LbOps(C.Structure):
     _fields_ = [("n_ops", I64), ("key_ptr", P), ("kind", P), ("id", P), ("score", P)]
+
+
+class LbRun(C.Structure):
+    """ccrdtx_lb_run (include/ccrdt_ext.h)."""
+    _fields_ = [("n_ops", I64), ("key", P), ("kind", P), ("id", P), ("score", P)]
 
 
 class LbExtra(C.Structure):
@@ -232,6 +243,9 @@ SIGNATURES = {
 EXT_SIGNATURES = {
     "ccrdtx_trmv_downstream_device": (INT, [P, C.POINTER(Requests), C.POINTER(TrmvOps), I64, I64, P]),
     "ccrdtx_lb_downstream_device": (INT, [P, C.POINTER(Requests), C.POINTER(LbOps), I64, P]),
+    "ccrdtx_lb_merge_runs_device": (INT, [P, INT, C.POINTER(LbRun), C.POINTER(LbOps), I64]),
+    "ccrdtx_lb_extras_run_device": (INT, [P, P, P, P, P, I64, C.POINTER(I64)]),
+    "ccrdtx_csr_keys_device": (INT, [P, P, I64, P]),
 }
 
 

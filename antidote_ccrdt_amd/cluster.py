@@ -1189,7 +1189,12 @@ class LbDeviceReplica(_DeviceReplica):
     sends; the exchange between them is injected: lb_replicate_step with a
     TorchCollective (one process per GPU) or lb_replicate_device_local
     (replicas held by one process, exchange = the list of every replica's
-    messages)."""
+    messages).  The merge of the gathered runs is done by
+    ccrdtx_lb_merge_runs_device, the extras come back as a run in stream order
+    from ccrdtx_lb_extras_run_device and the own batch's key column from
+    ccrdtx_csr_keys_device; torch only packs and unpacks columns.  The host
+    reads of a delivery are the gathered headers, the status records of the
+    merge and of the extras run, and apply_device's own."""
 
     def __init__(self, engine, rank: int, world: int):
         import torch
@@ -1197,28 +1202,50 @@ class LbDeviceReplica(_DeviceReplica):
         self.dev = torch.device("cuda", engine.device)
         self.msg = _LB_MSG
 
+    def _alloc(self, nbytes: int):
+        import torch
+        return _TensorBuf(torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.dev))
+
+    def _apply(self, db):
+        """apply_device(db) after torch's queued work; the extras (at most one
+        per op) as a run the codec takes.  The extras run's status read is the
+        wait after which torch may read what the engine stream wrote."""
+        import torch
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.dev))
+        self.engine.apply_device(db)
+        ex = self.engine.extras_run_device(db.n, alloc=self._alloc)
+        return None if ex is None else _lb_run(tuple(
+            _dev_tensor(ex.bufs[c], torch.int64, ex.n_ops, self.dev) for c in ex.COLUMNS))
+
     def originate(self, batch):
         """Apply this replica's own batch (device (key_ptr, kind, id, score),
         CSR by key, stream order) -- already canonical for one origin -- and
-        return its message: the batch, then its extras."""
+        return its message: the batch as a run, its key column expanded from
+        key_ptr, and then its extras."""
         import torch
         kp, kind, id_, score = batch
-        kp = kp.long()
-        n, nk = int(kind.shape[0]), int(kp.shape[0]) - 1
-        dev = kind.device
-        ex = _lb_apply_csr_device(self.engine, kp, kind.contiguous(), id_.contiguous(), score.contiguous())
-        keys = torch.repeat_interleave(torch.arange(nk, device=dev), kp[1:] - kp[:-1], output_size=n)
-        return self.msg.pack([_lb_run((keys, kind, id_, score)), _lb_run(ex)], self.dev)
+        kp, kind, id_, score = kp.long().contiguous(), kind.contiguous(), id_.contiguous(), score.contiguous()
+        n = int(kind.shape[0])
+        keys = torch.empty(n, dtype=torch.int64, device=self.dev)
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.dev))
+        self.engine.csr_keys_device(kp.data_ptr(), n, keys.data_ptr())
+        ex = self._apply(_TorchBatch(n, key_ptr=kp, kind=kind, id=id_, score=score))
+        return self.msg.pack([_lb_run((keys, kind, id_, score)), ex], self.dev)
 
     def deliver(self, rnd):
         """Apply the messages of every other origin (a round of read())
         merged into canonical order; returns the message of the extras that
         produced."""
-        runs = [tuple(cols) for _, cols, _ in self._runs(rnd)]
+        import torch
+
+        from .types import DeviceLbRun
+        runs = [DeviceLbRun.from_buffers(n, {c: _TensorBuf(t.contiguous()) for c, t in zip(DeviceLbRun.COLUMNS, cols)})
+                for (n,), cols, _ in self._runs(rnd)]
         if not runs:
             return self.msg.pack([], self.dev)
-        kp, kind, id_, sc = _lb_merge_runs(runs, self.engine.n_keys)
-        return self.msg.pack([_lb_run(_lb_apply_csr_device(self.engine, kp, kind, id_, sc))], self.dev)
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.dev))
+        merged = self.engine.merge_runs_device(runs, alloc=self._alloc)
+        return self.msg.pack([self._apply(merged)], self.dev)
 
 
 def lb_replicate_step(replica: LbDeviceReplica, batch, coll, max_rounds: int = 64) -> int:
@@ -1335,10 +1362,11 @@ class TrmvDeviceReplica(_DeviceReplica):
         import torch
 
         from .engine import DeviceTrmvRun
+        n = batch.n_ops
+        key = torch.empty(n, dtype=torch.int64, device=self.dev)
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.dev))
+        self.engine.csr_keys_device(batch.bufs["key_ptr"].p, n, key.data_ptr())  # (_apply's status reads wait for it)
         ex = self._apply(batch)
-        n, nk = batch.n_ops, self.engine.n_keys
-        kp = _dev_tensor(batch.bufs["key_ptr"], torch.int64, nk + 1, self.dev)
-        key = torch.repeat_interleave(torch.arange(nk, device=self.dev), kp[1:] - kp[:-1], output_size=n)
         own = DeviceTrmvRun.from_buffers(n, batch.n_rmv, {"key": _TensorBuf(key), **{
             c: batch.bufs[c] for c in DeviceTrmvRun.COLUMNS[1:]}}, batch.n_rmv_ops)
         return self._message([own, ex])

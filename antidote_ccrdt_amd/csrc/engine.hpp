@@ -130,6 +130,10 @@ struct ccrdt_engine {
   // scratch): by output position the op's source and key; the extras run's
   // per-key output offsets
   ccrdt::DevBuf rpl_src, rpl_key, rpl_off;
+  // leaderboard replication (lb_replicate_kernels.hip; the extras run shares
+  // rpl_off): the run merge's two u32 tables [n_runs][n_keys + 1], per run the
+  // ops below each key and each key's output base
+  ccrdt::DevBuf lbr_lower, lbr_base;
   int trmv_first_tier = 0;
   uint64_t last_n_ops = 0;
   uint64_t trmv_tot[2][3] = {};  // per side: bound on (players, pool, rows) held

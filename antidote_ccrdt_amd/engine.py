@@ -399,6 +399,12 @@ class _Engine:
                 "score": 8 * cap_ops, "dc": cap_ops, "ts": 8 * cap_ops, "rmv_vc": 8 * cap_rows * self.n_dc}
         return {n: alloc(size[n]) for n in names}
 
+    def csr_keys_device(self, d_key_ptr: int, n_ops: int, d_key: int) -> None:
+        """Enqueue the key column of a CSR resident in HBM (ccrdtx_csr_keys_device):
+        device int64[n_ops] at d_key, entry i = the key whose range of the
+        device uint64[n_keys + 1] at d_key_ptr holds i.  No wait."""
+        check(lib.ccrdtx_csr_keys_device(self.h, d_key_ptr, int(n_ops), d_key), "csr_keys_device")
+
     def _values(self, name: str, keys):
         """ccrdt_<name>_value over `keys` (None: every key): (ptr uint64[n + 1],
         id int64, score int64), each key's pairs ranked by cmp/2."""

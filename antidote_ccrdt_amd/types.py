@@ -154,6 +154,38 @@ class LbState:
                 "min": [int(self.min_id[k]), int(self.min_score[k])] if self.min_valid[k] else None}
 
 
+class DeviceLbRun:
+    """A run of leaderboard effects resident in HBM (ccrdtx_lb_run): effects
+    of one origin in its sequence order, sorted by key; four int64 columns, as
+    the run message carries them."""
+    COLUMNS = ("key", "kind", "id", "score")
+
+    def __init__(self, key, kind, id, score):
+        from .engine import DeviceArray
+        self._set(len(key), {n: DeviceArray(_c(v, np.int64)) for n, v in zip(self.COLUMNS, (key, kind, id, score))})
+
+    def _set(self, n_ops: int, bufs: dict) -> None:
+        self.n_ops, self.bufs = int(n_ops), bufs
+        self.c = _lib.LbRun(self.n_ops, *[bufs[n].p for n in self.COLUMNS])
+
+    @classmethod
+    def from_buffers(cls, n_ops: int, bufs: dict) -> "DeviceLbRun":
+        """A run over device buffers that already hold it: bufs maps every
+        name of COLUMNS to a buffer with a device pointer `.p`, which the run
+        owns from here on."""
+        d = cls.__new__(cls)
+        d._set(n_ops, bufs)
+        return d
+
+    def to_host(self) -> tuple:
+        """(key, kind, id, score) copied back to the host."""
+        return tuple(self.bufs[c].to_host(np.int64, self.n_ops) for c in self.COLUMNS)
+
+    def close(self):
+        for d in self.bufs.values():
+            d.close()
+
+
 class LeaderboardEngine(_Engine):
     """antidote_ccrdt_leaderboard (src/antidote_ccrdt_leaderboard.erl)."""
     TYPE = _lib.LEADERBOARD
@@ -220,6 +252,54 @@ class LeaderboardEngine(_Engine):
             raise
         out.n = int(co.n_ops)
         return (out, kinds) if want_kinds else out
+
+    def merge_runs_device(self, runs, cap_ops: int | None = None, alloc=None) -> "DeviceBatch":
+        """1 .. _lib.LB_MAX_RUNS DeviceLbRuns, given in (origin, sequence)
+        order, merged on the device into the one batch of the canonical order
+        (key, origin, seq) (ccrdtx_lb_merge_runs_device), which apply_device
+        and compact_device take as it is (n = its op count).  cap_ops defaults
+        to the runs' op total; a result over it raises CcrdtError(ENOMEM) with
+        `totals`.  `alloc` (bytes -> a buffer with `.p` and `.close()`)
+        provides the outputs."""
+        from .engine import DeviceArray
+        runs = list(runs)
+        cap_ops = sum(r.n_ops for r in runs) if cap_ops is None else int(cap_ops)
+        out = DeviceBatch.from_buffers(0, self._op_bufs(("key_ptr", "kind", "id", "score"), cap_ops, 0,
+                                                        alloc or DeviceArray.empty))
+        co = _lib.LbOps(0, out["key_ptr"], out["kind"], out["id"], out["score"])
+        cr = (_lib.LbRun * max(len(runs), 1))(*[r.c for r in runs])
+        try:
+            check(lib.ccrdtx_lb_merge_runs_device(self.h, len(runs), cr, C.byref(co), cap_ops), "lb_merge_runs_device")
+        except _lib.CcrdtError as err:
+            err.totals = (int(co.n_ops), 0)
+            out.close()
+            raise
+        out.n = int(co.n_ops)
+        return out
+
+    def extras_run_device(self, cap_ops: int, alloc=None) -> DeviceLbRun | None:
+        """The last apply's extra effects as a run in (key, op index) order,
+        on the device (ccrdtx_lb_extras_run_device): the stream order the host
+        protocol re-broadcasts them in; None when there are none.  cap_ops: a
+        bound the caller knows (an op has at most one extra); a result over it
+        raises CcrdtError(ENOMEM) with `totals`."""
+        from .engine import DeviceArray
+        cap_ops = int(cap_ops)
+        bufs = {c: (alloc or DeviceArray.empty)(8 * cap_ops) for c in DeviceLbRun.COLUMNS}
+        n = C.c_int64(0)
+        try:
+            check(lib.ccrdtx_lb_extras_run_device(self.h, *[bufs[c].p for c in DeviceLbRun.COLUMNS], cap_ops,
+                                                  C.byref(n)), "lb_extras_run_device")
+        except _lib.CcrdtError as err:
+            err.totals = (int(n.value), 0)
+            for d in bufs.values():
+                d.close()
+            raise
+        if not n.value:
+            for d in bufs.values():
+                d.close()
+            return None
+        return DeviceLbRun.from_buffers(int(n.value), bufs)
 
     def values(self, keys=None):
         """value/1 (leaderboard.erl:84-86) of `keys` (board indices in any

@@ -58,6 +58,65 @@ int ccrdtx_trmv_downstream_device(ccrdt_engine* e, const ccrdtx_requests* dev_re
 int ccrdtx_lb_downstream_device(ccrdt_engine* e, const ccrdtx_requests* dev_req, ccrdt_lb_batch* dev_out,
                                 int64_t cap_ops, uint8_t* d_req_kind);
 
+/* A run of leaderboard effects: what one replica contributes to a delivery of
+ * the replication mode -- effects of one origin in that origin's sequence
+ * order, sorted by key (non-decreasing).  COO: key[i] is op i's key.  Every
+ * column is int64 words, as the run message carries it. */
+typedef struct {
+  int64_t n_ops;
+  const int64_t* key;   /* [n_ops] non-decreasing, in [0, n_keys) */
+  const int64_t* kind;  /* [n_ops] CCRDT_LB_*, one int64 word each */
+  const int64_t* id;    /* [n_ops] */
+  const int64_t* score; /* [n_ops] (ignored for ban) */
+} ccrdtx_lb_run;
+/* Runs per merge; ops of one run a workgroup of the merge takes. */
+#define CCRDTX_LB_MAX_RUNS 32
+#define CCRDTX_LB_MERGE_TILE 256
+/* n_runs runs, given in (origin, sequence) order, merged on the device into
+ * the one CSR batch of the canonical order (key, origin, seq): per key run 0's
+ * ops of that key, then run 1's, and so on, each run's own order kept (what
+ * the host protocol gets by sorting the gathered rows, cluster.canonical, and
+ * rebuilding the CSR).  dev_runs is a host array of n_runs structs whose n_ops
+ * are host values and whose array pointers are device memory; dev_out is laid
+ * out as for ccrdt_lb_compact_device (cap_ops ops, key_ptr n_keys + 1 entries)
+ * and must not overlap a run.  n_keys is the engine's.  kind is narrowed to
+ * uint8 and a ban's score is 0, so the result can be handed to
+ * ccrdt_lb_apply_device (or ccrdt_lb_compact_device) as it is.  The merge
+ * counts instead of searching: it keeps two engine-owned tables of n_runs *
+ * (n_keys + 1) 32-bit words (8 * n_runs * (n_keys + 1) bytes in all).  The
+ * work is enqueued on the engine stream; the call then reads back one small
+ * status record (op total, error word), its only wait, and sets dev_out->n_ops
+ * from it.  The engine's resident state is neither read nor changed.
+ * CCRDT_ENOMEM: the op total exceeds cap_ops; the true total is still set,
+ * key_ptr[0 .. n_keys] is written in full and nothing at or past the capacity
+ * is written.  CCRDT_EINVAL, with nothing written to dev_out's arrays: a run
+ * whose keys decrease, a key outside [0, n_keys), a kind outside 0..2, null
+ * arrays with n_ops > 0, 2^32 ops or more in all, n_runs outside [1,
+ * CCRDTX_LB_MAX_RUNS], a null engine, an engine of another type.  After any
+ * error the engine stays usable.  No ops in any run is valid: all of key_ptr
+ * is 0. */
+int ccrdtx_lb_merge_runs_device(ccrdt_engine* e, int n_runs, const ccrdtx_lb_run* dev_runs, ccrdt_lb_batch* dev_out,
+                                int64_t cap_ops);
+
+/* The extra effects of the last ccrdt_lb_apply / _apply_device as a run, in
+ * (key, op index) order -- the stream order the host protocol re-broadcasts
+ * them in.  The four device columns (cap_ops int64 words each) are ready for
+ * the run message: effect i's key, its kind (always CCRDT_LB_ADD = {add, {Id,
+ * Score}}, leaderboard.erl:282-284), id and score.  Enqueued on the engine
+ * stream after the apply; the status read-back, *n_ops, CCRDT_ENOMEM with the
+ * true total and nothing written at or past the capacity are as for
+ * ccrdtx_lb_merge_runs_device.  No extras (or no apply yet) is valid: *n_ops =
+ * 0.  The resident state and the extras themselves are not changed
+ * (ccrdt_lb_fetch_extra / _extras_device still serve them). */
+int ccrdtx_lb_extras_run_device(ccrdt_engine* e, int64_t* d_key, int64_t* d_kind, int64_t* d_id, int64_t* d_score,
+                                int64_t cap_ops, int64_t* n_ops);
+
+/* The key column of a CSR: d_key[i] = k iff d_key_ptr[k] <= i < d_key_ptr[k+1],
+ * for i in [0, n_ops).  d_key_ptr (device) has the engine's n_keys + 1 entries
+ * and ends at n_ops; d_key (device) has n_ops.  An engine of any type.  The
+ * work is only enqueued on the engine stream: the call does not wait. */
+int ccrdtx_csr_keys_device(ccrdt_engine* e, const uint64_t* d_key_ptr, int64_t n_ops, int64_t* d_key);
+
 #ifdef __cplusplus
 }
 #endif
