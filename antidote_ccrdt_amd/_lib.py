@@ -30,6 +30,12 @@ LB_MERGE_TILE = 256
 # the key column (ccrdtx_csr_keys_device): output positions per workgroup, keys of key_ptr it stages at a time
 CSR_KEYS_TILE = 1024
 CSR_KEYS_WIN = 1024
+# the partition by key owner (ccrdtx_trmv_partition_device): parts per call, source keys of a key tile and input ops
+# of an op tile, key_ptr entries an op tile stages in LDS, the "leave this key's ops out" bit of d_local
+TRMV_MAX_PARTS = 32
+TRMV_PART_TILE = 256
+TRMV_PART_WIN = 1024
+TRMV_PART_DROP = 1 << 31
 
 P = C.c_void_p
 I64 = C.c_int64
@@ -90,6 +96,12 @@ class TrmvState(C.Structure):
                 ("obs_dc", P), ("m_ptr", P), ("m_id", P), ("m_score", P), ("m_ts", P),
                 ("m_dc", P), ("r_ptr", P), ("r_id", P), ("r_vc", P), ("min_valid", P),
                 ("min_id", P), ("min_score", P), ("min_ts", P), ("min_dc", P)]
+
+
+class TrmvParts(C.Structure):
+    """ccrdtx_trmv_parts (include/ccrdt_ext.h)."""
+    _fields_ = [("key", P), ("kind", P), ("id", P), ("score", P), ("dc", P), ("ts", P), ("rmv_vc", P),
+                ("src_op", P), ("key_ptr", P)]
 
 
 class Requests(C.Structure):
@@ -246,6 +258,8 @@ EXT_SIGNATURES = {
     "ccrdtx_lb_merge_runs_device": (INT, [P, INT, C.POINTER(LbRun), C.POINTER(LbOps), I64]),
     "ccrdtx_lb_extras_run_device": (INT, [P, P, P, P, P, I64, C.POINTER(I64)]),
     "ccrdtx_csr_keys_device": (INT, [P, P, I64, P]),
+    "ccrdtx_trmv_partition_device": (INT, [P, I64, C.POINTER(TrmvOps), INT, INT, P, P, C.POINTER(TrmvParts), I64, I64,
+                                           P, P, P]),
 }
 
 

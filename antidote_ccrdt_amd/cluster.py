@@ -84,6 +84,41 @@ def route(batch: TrmvBatch, keys: np.ndarray, drop=()) -> Shard:
     return Shard(keys, sub, op_index)
 
 
+class ShardMap:
+    """Where every key of a keyspace goes, resident in HBM for
+    TopkRmvEngine.partition_device: d_part int32[n_keys] the key's part,
+    d_local uint32[n_keys] its id in that part's keyspace (dense, ascending
+    with the key), bit 31 set for a key whose ops are left out (a host-path
+    key).  keys[p]: the global ids of part p, ascending (keys[p][j] has id j).
+    Built once per keyspace; drop() marks keys afterwards."""
+
+    def __init__(self, part, n_parts: int):
+        from . import _lib
+        from .engine import DeviceArray
+        part = np.ascontiguousarray(part, np.int32)
+        self.n_keys, self.n_parts = int(part.shape[0]), int(n_parts)
+        order = np.argsort(part, kind="stable")
+        counts = np.bincount(part, minlength=self.n_parts)
+        ends = np.cumsum(counts)
+        self.keys = np.split(order.astype(np.int64), ends[:-1])
+        self.local = np.empty(self.n_keys, np.uint32)
+        self.local[order] = np.arange(self.n_keys) - np.repeat(ends - counts, counts)
+        self.drop_bit = np.uint32(_lib.TRMV_PART_DROP)
+        self.d_part, self.d_local = DeviceArray(part), DeviceArray(self.local)
+
+    @classmethod
+    def of_owner(cls, n_keys: int, world: int) -> "ShardMap":
+        """The map of the key sharding: part = owner(key)."""
+        return cls(owner(np.arange(n_keys, dtype=np.uint64), world), world)
+
+    def drop(self, keys) -> None:
+        """Leave the ops of these (global) keys out from now on."""
+        from . import _lib
+        self.local[np.asarray(keys, np.int64)] |= self.drop_bit
+        if self.n_keys:
+            _lib.check(_lib.lib.ccrdt_memcpy_h2d(self.d_local.p, _lib.ptr(self.local), self.local.nbytes), "h2d")
+
+
 def _drop_keys(batch: TrmvBatch, drop: np.ndarray) -> TrmvBatch:
     """The batch without the ops of the (local) keys in `drop`."""
     return route(batch, np.arange(batch.key_ptr.shape[0] - 1), drop).batch
@@ -397,6 +432,77 @@ class ShardedTopkRmv:
             coll = TorchCollective(dist)
         self.coll = coll
         self.xchg = TrmvShardExchange(n_dc, coll, device if self.on_device else None)
+        self.map = None        # the keyspace's ShardMap, built by the first device routing
+        self._mapped = set()   # the host-path keys marked in it
+
+    def _shard_map(self) -> ShardMap:
+        """The keyspace's map on the device, every host-path key marked."""
+        if self.map is None:
+            self.map = ShardMap.of_owner(self.n_keys, self.world)
+        new = self.host_keys - self._mapped
+        if new:
+            self.map.drop(sorted(new))
+            self._mapped |= new
+        return self.map
+
+    def _alloc(self, nbytes: int):
+        import torch
+        return _TensorBuf(torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.xchg.dev))
+
+    def route_device(self, db):
+        """route() of a DeviceTrmvBatch over the global keyspace, in HBM
+        (TopkRmvEngine.partition_device with only = this rank): (this rank's
+        sub-batch as a DeviceTrmvBatch over its keys, op_index as a device
+        int64 tensor).  The partition's status read is its only wait."""
+        import torch
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.xchg.dev))
+        sub, src = self.engine.partition_device(db, self._shard_map(), only=self.rank, alloc=self._alloc)
+        return sub, _dev_tensor(src, torch.int64, sub.n_ops, self.xchg.dev)
+
+    def _ingest_send(self, db):
+        """The partition of a batch this rank holds for keys of every owner:
+        (one flat int64 tensor, the messages to rank 0, 1, ... back to back in
+        the run format of _trmv_msg; each message's length)."""
+        import torch
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.xchg.dev))
+        parts, src = self.engine.partition_device(db, self._shard_map(), alloc=self._alloc)
+        msg = _trmv_msg(self.n_dc)
+        out = [msg.pack([_trmv_run(r, self.n_dc, self.xchg.dev)], self.xchg.dev) for r in parts]
+        return torch.cat(out), [int(m.shape[0]) for m in out]
+
+    def _ingest_recv(self, recv, sizes):
+        """Merge the messages received (recv: the messages of rank 0, 1, ...
+        back to back, `sizes` their lengths) in source-rank order and apply the
+        result; returns the merged DeviceTrmvBatch, or None when no op arrived."""
+        import torch
+
+        from .engine import DeviceTrmvRun
+        msg = _trmv_msg(self.n_dc)
+        at = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        msgs = [recv[int(a):int(b)] for a, b in zip(at[:-1], at[1:])]
+        hdrs, _ = msg.headers(msgs)
+        runs = [DeviceTrmvRun.from_buffers(n, rows, {c: _TensorBuf(t.contiguous()) for c, t in
+                                                     zip(DeviceTrmvRun.COLUMNS, (*cols, block))}, n_rmv_ops)
+                for m, h in zip(msgs, hdrs) if h is not None
+                for (n, rows, n_rmv_ops), cols, block in msg.unpack(m.to(self.xchg.dev), h)]
+        if not runs:
+            return None
+        _engine_stream(self.engine).wait_stream(torch.cuda.current_stream(self.xchg.dev))
+        merged = self.engine.merge_runs_device(runs, alloc=self._alloc)
+        self.apply_device(merged)
+        return merged
+
+    def ingest_device(self, db, a2a):
+        """A batch this rank holds (DeviceTrmvBatch over the global keyspace:
+        effects it made with downstream_device from the requests it received)
+        sent to the keys' owners and applied there, all in HBM: the partition
+        by owner, one message per destination, the injected variable
+        all-to-all (TorchCollective.all_to_all_v), the run merge of what
+        arrived in source-rank order, apply_device.  A key's ops are applied
+        in the order source rank, then the source's stream order.  Returns the
+        merged batch this rank applied (None: no op arrived)."""
+        send, splits = self._ingest_send(db)
+        return self._ingest_recv(*a2a(send, splits))
 
     def route(self, batch: TrmvBatch) -> Shard:
         """This rank's sub-batch of a global batch (host-path keys' ops left out)."""
@@ -434,8 +540,9 @@ class ShardedTopkRmv:
         vc = st["vc"] if isinstance(st, dict) else st.vc
         return vc.max(axis=0) if vc.shape[0] else np.zeros(self.n_dc, np.int64)
 
-    def step(self, batch: TrmvBatch):
-        """One batch: apply this rank's keys, then the exchange.  Returns
+    def step(self, batch):
+        """One batch (a TrmvBatch, or with the HIP engine a DeviceTrmvBatch,
+        over the global keyspace): apply this rank's keys, then the exchange.  Returns
         (every rank's extras as int64 rows in global stream order, the
         replica Vc), numpy, identical on every rank.  A rank whose apply
         raises (an invalid op among its keys, a device error) still takes
@@ -449,10 +556,13 @@ class ShardedTopkRmv:
                 import torch
 
                 from .engine import DeviceTrmvBatch
-                sh = self.route(batch)
-                db = DeviceTrmvBatch(sh.batch)
+                if isinstance(batch, DeviceTrmvBatch):  # already in HBM: routed there
+                    db, op_index = self.route_device(batch)
+                else:
+                    sh = self.route(batch)
+                    db, op_index = DeviceTrmvBatch(sh.batch), torch.from_numpy(sh.op_index).to(self.xchg.dev)
                 try:
-                    self.apply_device(db, torch.from_numpy(sh.op_index).to(self.xchg.dev))
+                    self.apply_device(db, op_index)
                 finally:
                     db.close()
             else:
@@ -1404,3 +1514,17 @@ def trmv_replicate_device_local(engines, batches, max_rounds: int = 64) -> int:
     KeyCapacityError of a replica's apply_device propagates once every replica
     has applied the round."""
     return _replicate([TrmvDeviceReplica(e, r, len(engines)) for r, e in enumerate(engines)], batches, None, max_rounds)
+
+
+def sharded_ingest_device_local(shards, dbs):
+    """ShardedTopkRmv.ingest_device for the shards of a keyspace held by one
+    process (the all-to-all done by slicing): dbs[r] is the DeviceTrmvBatch
+    rank r holds, over the global keyspace.  Returns each shard's merged batch
+    (None where no op arrived)."""
+    import torch
+    sent = [s._ingest_send(db) for s, db in zip(shards, dbs)]
+    out = []
+    for dst, s in enumerate(shards):
+        parts = [send[sum(sp[:dst]):sum(sp[:dst + 1])] for send, sp in sent]
+        out.append(s._ingest_recv(torch.cat(parts), [int(p.shape[0]) for p in parts]))
+    return out

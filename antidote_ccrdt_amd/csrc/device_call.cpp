@@ -57,17 +57,18 @@ int upload_keys(Engine& E, int64_t n, const uint64_t* keys, DevBuf& buf, const c
   return CCRDT_OK;
 }
 
-int status_clear(Engine& E, uint64_t** dev) {
-  CCRDT_TRY(E.call_status.ensure(ST_WORDS * 8));
+int status_clear(Engine& E, uint64_t** dev, int extra_words) {
+  CCRDT_TRY(E.call_status.ensure((uint64_t)(ST_WORDS + extra_words) * 8));
   *dev = E.call_status.as<uint64_t>();
-  CCRDT_HIP(hipMemsetAsync(*dev, 0, ST_WORDS * 8, E.stream));
+  CCRDT_HIP(hipMemsetAsync(*dev, 0, (size_t)(ST_WORDS + extra_words) * 8, E.stream));
   return CCRDT_OK;
 }
 
 int status_finish(Engine& E, uint64_t cap_ops, uint64_t cap_rows, int64_t* n_ops, int64_t* n_rows, const char* where,
-                  const char* msg_shape, const char* msg_op) {
-  uint64_t st[ST_WORDS];
-  CCRDT_TRY(read_back(E, st, E.call_status.p));
+                  const char* msg_shape, const char* msg_op, uint64_t* extra, int extra_words) {
+  uint64_t st[H_STATUS_BYTES / 8];
+  CCRDT_TRY(read_back(E, st, E.call_status.p, (size_t)(ST_WORDS + extra_words) * 8));
+  if (extra) memcpy(extra, st + ST_WORDS, (size_t)extra_words * 8);
   if (n_ops) *n_ops = (int64_t)st[ST_OPS];
   if (n_rows) *n_rows = (int64_t)st[ST_ROWS];
   if (st[ST_ERR]) {

@@ -43,12 +43,16 @@ constexpr uint64_t ST_ERR_SHAPE = 2;  // the module's own: the batch's CSR, or t
 // Topk_rmv's text for ST_ERR_OP.
 constexpr const char* ST_TRMV_OP = ": effect kind > 3, rmv clock row out of range, or add DC rank >= n_dc";
 // The record allocated and cleared on E.stream: *dev = its device address.
-int status_clear(Engine& E, uint64_t** dev);
+// extra_words: words of the call's own behind the record (the partition's
+// per-part totals), cleared and read back with it.
+int status_clear(Engine& E, uint64_t** dev, int extra_words = 0);
 // The record read back (the call's only wait).  The totals go to *n_ops and
 // *n_rows (null: not wanted) whatever the outcome; ST_ERR_SHAPE is
 // CCRDT_EINVAL with msg_shape, another error bit CCRDT_EINVAL with msg_op,
-// totals over a capacity CCRDT_ENOMEM (the totals are the true ones).
+// totals over a capacity CCRDT_ENOMEM (the totals are the true ones).  extra:
+// where status_clear's extra words go, whatever the outcome.
 int status_finish(Engine& E, uint64_t cap_ops, uint64_t cap_rows, int64_t* n_ops, int64_t* n_rows, const char* where,
-                  const char* msg_shape, const char* msg_op = ST_TRMV_OP);
+                  const char* msg_shape, const char* msg_op = ST_TRMV_OP, uint64_t* extra = nullptr,
+                  int extra_words = 0);
 
 }  // namespace ccrdt

@@ -8,7 +8,7 @@
 
 namespace ccrdt {
 
-constexpr size_t H_STATUS_BYTES = 256;  // the engine's pinned read-back block (h_status)
+constexpr size_t H_STATUS_BYTES = 512;  // the engine's pinned read-back block (h_status)
 
 // One ping-pong side of GPU-resident topk_rmv state (trmv_kernels.hpp): the
 // meta + cap arrays of meta index s and the data arrays of data index s
@@ -134,6 +134,10 @@ struct ccrdt_engine {
   // rpl_off): the run merge's two u32 tables [n_runs][n_keys + 1], per run the
   // ops below each key and each key's output base
   ccrdt::DevBuf lbr_lower, lbr_base;
+  // batch partition by key owner (partition_kernels.hip; it shares the
+  // compaction's and the replication's scratch): the (part, key tile) counts
+  // of ops and of clock rows
+  ccrdt::DevBuf pt_cnt;
   int trmv_first_tier = 0;
   uint64_t last_n_ops = 0;
   uint64_t trmv_tot[2][3] = {};  // per side: bound on (players, pool, rows) held

@@ -41,42 +41,6 @@ namespace ccrdt {
 
 namespace {
 
-// First index of v[0 .. n) whose value is > k (UPPER) or >= k (v non-decreasing).
-template <bool UPPER, class T>
-__device__ __forceinline__ uint32_t rpl_bound(const T* v, uint32_t n, T k) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    const T x = v[mid];
-    if (UPPER ? x <= k : x < k) {
-      lo = mid + 1;
-    } else {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
-// The wave's clock rows, 8 lanes per row (the row shape tier 0 writes): a lane
-// with `has` hands over its source row and its output row through the wave's
-// LDS slots; the wave then copies 8 rows at a time.  Every lane of the wave
-// must call it.
-__device__ __forceinline__ void rpl_copy_rows(bool has, const int64_t* srow, uint64_t drow, int64_t* o_vc, uint32_t D,
-                                              uint64_t* s_src, uint64_t* s_dst) {
-  const uint64_t m = ballot(has);
-  if (!m) return;
-  if (has) {
-    const uint32_t q = mbcnt(m);
-    s_src[q] = reinterpret_cast<uint64_t>(srow);
-    s_dst[q] = drow;
-  }
-  wave_lds_sync();
-  const uint32_t cnt = (uint32_t)__popcll(m), d = (uint32_t)lane_id() & 7u;
-  for (uint32_t q = (uint32_t)lane_id() >> 3; q < cnt; q += 8)
-    if (d < D) o_vc[s_dst[q] * D + d] = reinterpret_cast<const int64_t*>(s_src[q])[d];
-  wave_lds_sync();
-}
-
 // ---------------------------------------------------------------- merge: rank
 __global__ __launch_bounds__(RPL_TILE) void trmv_merge_rank_kernel(MergeArgs) {
   const auto ka = kernarg_as<MergeArgs>();

@@ -223,6 +223,20 @@ class DeviceArray:
             pass
 
 
+class DeviceSlice:
+    """Bytes [off, off + nbytes) of a device buffer as a buffer of their own
+    (`.p`, `.to_host`): it keeps the base buffer alive and close() leaves the
+    base to its owner."""
+
+    def __init__(self, base, off: int, nbytes: int):
+        self.base, self.p, self.nbytes = base, base.p + int(off), int(nbytes)
+
+    to_host = DeviceArray.to_host
+
+    def close(self):
+        self.base = self.p = None
+
+
 class _DeviceTrmvColumns:
     """Topk_rmv ops resident in HBM: one device buffer per name of COLUMNS,
     which are the pointer fields of the ctypes struct CSTRUCT, in its order."""
@@ -560,6 +574,52 @@ class TopkRmvEngine(_Engine):
         self._sized_call(lib.ccrdt_trmv_merge_runs_device, "trmv_merge_runs_device", co, bufs, len(runs), cr,
                          C.byref(co), int(cap_ops), int(cap_rows))
         return DeviceTrmvBatch.from_buffers(co.n_ops, co.n_rmv_rows, bufs, n_rmv_ops=co.n_rmv_rows)
+
+    def partition_device(self, db: DeviceTrmvBatch, shard_map, only: int = -1, alloc=None):
+        """A batch resident in HBM split by key owner on the device
+        (ccrdtx_trmv_partition_device): part p is cluster.route(batch, keys of
+        part p, dropped keys).batch.  shard_map (cluster.ShardMap, or any object
+        with n_keys, n_parts and the device buffers d_part, d_local) covers
+        db's keyspace; the engine only lends its stream and scratch.  Returns
+        (parts, src_op): the parts as DeviceTrmvRuns over slices of one buffer
+        per column, each with its own CSR as `.key_ptr` (a device buffer of its
+        keys + 1 entries), and the device buffer int64[n_ops kept] of every
+        output op's index in db.  only >= 0: that part alone, as a
+        DeviceTrmvBatch (CSR over the part's keys) that apply_device takes as
+        it is, and its src_op.  `alloc` (bytes -> a buffer with `.p` and
+        `.close()`) provides the outputs."""
+        alloc = alloc or DeviceArray.empty
+        P, nk = int(shard_map.n_parts), int(shard_map.n_keys)
+        cap_ops, cap_rows = db.n_ops, db.n_ops if db.n_rmv_ops is None else db.n_rmv_ops
+        names = [f[0] for f in _lib.TrmvParts._fields_ if only < 0 or f[0] != "key"]
+        item = {"key": 8, "kind": 1, "id": 8, "score": 8, "dc": 1, "ts": 8, "rmv_vc": 8 * self.n_dc, "src_op": 8}
+        bufs = {n: alloc(8 * (nk + P) if n == "key_ptr" else item[n] * (cap_rows if n == "rmv_vc" else cap_ops))
+                for n in names}
+        co = _lib.TrmvParts(*[bufs[f[0]].p if f[0] in bufs else None for f in _lib.TrmvParts._fields_])
+        ops, rows, kb = np.zeros(P, np.int64), np.zeros(P, np.int64), np.zeros(P + 1, np.int64)
+        try:
+            check(lib.ccrdtx_trmv_partition_device(self.h, nk, C.byref(db.c), P, int(only), shard_map.d_part.p,
+                                                   shard_map.d_local.p, C.byref(co), cap_ops, cap_rows, ptr(ops),
+                                                   ptr(rows), ptr(kb)), "trmv_partition_device")
+        except _lib.CcrdtError as err:
+            err.totals = (int(ops.sum()), int(rows.sum()))
+            for d in bufs.values():
+                d.close()
+            raise
+        src_op = bufs.pop("src_op")
+        if only >= 0:
+            n, r = int(ops[only]), int(rows[only])
+            return DeviceTrmvBatch.from_buffers(n, r, bufs, n_rmv_ops=r), src_op
+        o0, r0 = np.concatenate([[0], np.cumsum(ops)]), np.concatenate([[0], np.cumsum(rows)])
+        parts = []
+        for p in range(P):
+            n, r = int(ops[p]), int(rows[p])
+            run = DeviceTrmvRun.from_buffers(n, r, {c: DeviceSlice(bufs[c], int(r0[p] if c == "rmv_vc" else o0[p]) *
+                                                                   item[c], (r if c == "rmv_vc" else n) * item[c])
+                                                    for c in DeviceTrmvRun.COLUMNS}, n_rmv_ops=r)
+            run.key_ptr = DeviceSlice(bufs["key_ptr"], 8 * int(kb[p]), 8 * int(kb[p + 1] - kb[p]))
+            parts.append(run)
+        return parts, src_op
 
     def extras_run_device(self, cap_ops: int | None = None, cap_rows: int | None = None,
                           alloc=DeviceArray.empty) -> DeviceTrmvRun | None:

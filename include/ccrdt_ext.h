@@ -117,6 +117,57 @@ int ccrdtx_lb_extras_run_device(ccrdt_engine* e, int64_t* d_key, int64_t* d_kind
  * work is only enqueued on the engine stream: the call does not wait. */
 int ccrdtx_csr_keys_device(ccrdt_engine* e, const uint64_t* d_key_ptr, int64_t n_ops, int64_t* d_key);
 
+/* The output columns of ccrdtx_trmv_partition_device, all device memory: the
+ * parts lie back to back in them.  key[o] is output op o's key in its part's
+ * keyspace, src_op[o] its index in the source batch; key_ptr holds every
+ * part's own CSR (from 0), part p's at part_keys_base[p].  key, src_op and
+ * key_ptr may each be NULL: not wanted. */
+typedef struct {
+  int64_t* key;      /* [cap_ops] */
+  uint8_t* kind;     /* [cap_ops] */
+  int64_t* id;       /* [cap_ops] */
+  int64_t* score;    /* [cap_ops] */
+  uint8_t* dc;       /* [cap_ops] */
+  int64_t* ts;       /* [cap_ops] */
+  int64_t* rmv_vc;   /* [cap_rows * n_dc] */
+  int64_t* src_op;   /* [cap_ops] */
+  uint64_t* key_ptr; /* [n_src_keys + n_parts] */
+} ccrdtx_trmv_parts;
+/* Parts per call; source keys of a key tile and input ops of an op tile; the
+ * key_ptr entries an op tile stages in LDS. */
+#define CCRDTX_TRMV_MAX_PARTS 32
+#define CCRDTX_TRMV_PART_TILE 256
+#define CCRDTX_TRMV_PART_WIN 1024
+/* A stable split of one effect batch resident in HBM (dev_in: a CSR over
+ * n_src_keys keys, n_ops and n_rmv_rows host values, arrays device memory)
+ * into n_parts key-sorted runs: source key k goes to part d_part[k] (device,
+ * int32[n_src_keys]) as key d_local[k] & 0x7fffffff of that part (device,
+ * uint32[n_src_keys]; the ids of a part are dense and ascend with k); bit 31 of
+ * d_local[k] set: the key's ops are left out and it keeps an empty range.
+ * Part p is what cluster.route gives for its keys: each key's ops in stream
+ * order, every rmv with a clock row of its own numbered from 0 inside the part
+ * (ts = that row), score and dc as given.  Part p's ops are output ops
+ * [sum part_ops[< p], + part_ops[p]), its clock rows likewise by part_rows,
+ * its key_ptr the part_keys_base[p + 1] - part_keys_base[p] entries (its keys
+ * + 1) from part_keys_base[p]; the three are host arrays of n_parts, n_parts
+ * and n_parts + 1 entries.  only >= 0: only that part is produced, at offset
+ * 0, and the other parts' totals are 0.  The engine is any topk_rmv engine
+ * (n_dc is its; its state is neither read nor changed).  The work is enqueued
+ * on the engine stream; the call then reads back one status record carrying
+ * the totals, its only wait.  CCRDT_ENOMEM: the op total exceeds cap_ops or
+ * the row total cap_rows; the true totals are set and nothing at or past a
+ * capacity is written.  CCRDT_EINVAL, with nothing written: a kind above 3, a
+ * rmv clock row outside [0, n_rmv_rows) (the row is not read), a key_ptr that
+ * is not monotone from 0 to n_ops, a part outside [0, n_parts), local ids past
+ * key_ptr's room, 2^32 ops or more, null arrays with n_ops > 0, n_parts
+ * outside [1, CCRDTX_TRMV_MAX_PARTS], only outside [-1, n_parts), a null
+ * engine or one of another type.  After any error the engine stays usable.
+ * n_ops == 0 is valid (dev_in's op arrays may then be NULL). */
+int ccrdtx_trmv_partition_device(ccrdt_engine* e, int64_t n_src_keys, const ccrdt_trmv_ops* dev_in, int n_parts,
+                                 int only, const int32_t* d_part, const uint32_t* d_local,
+                                 const ccrdtx_trmv_parts* dev_out, int64_t cap_ops, int64_t cap_rows,
+                                 int64_t* part_ops, int64_t* part_rows, int64_t* part_keys_base);
+
 #ifdef __cplusplus
 }
 #endif
