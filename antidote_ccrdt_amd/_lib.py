@@ -36,6 +36,11 @@ TRMV_MAX_PARTS = 32
 TRMV_PART_TILE = 256
 TRMV_PART_WIN = 1024
 TRMV_PART_DROP = 1 << 31
+# the group by key (ccrdtx_group_by_key_device): ops of a workgroup tile, key bits per pass; columns per
+# ccrdtx_gather_device call
+GROUP_TILE = 2048
+GROUP_BITS = 8
+GATHER_MAX_COLS = 8
 
 P = C.c_void_p
 I64 = C.c_int64
@@ -107,6 +112,11 @@ class TrmvParts(C.Structure):
 class Requests(C.Structure):
     """ccrdtx_requests (include/ccrdt_ext.h)."""
     _fields_ = [("n_req", I64), ("key_ptr", P), ("op", P), ("id", P), ("score", P), ("dc", P), ("ts", P)]
+
+
+class Column(C.Structure):
+    """ccrdtx_column (include/ccrdt_ext.h)."""
+    _fields_ = [("in_", P), ("out", P), ("width", C.c_int32)]
 
 
 class AvgOps(C.Structure):
@@ -260,6 +270,8 @@ EXT_SIGNATURES = {
     "ccrdtx_csr_keys_device": (INT, [P, P, I64, P]),
     "ccrdtx_trmv_partition_device": (INT, [P, I64, C.POINTER(TrmvOps), INT, INT, P, P, C.POINTER(TrmvParts), I64, I64,
                                            P, P, P]),
+    "ccrdtx_group_by_key_device": (INT, [P, I64, P, P, P]),
+    "ccrdtx_gather_device": (INT, [P, I64, P, INT, C.POINTER(Column)]),
 }
 
 

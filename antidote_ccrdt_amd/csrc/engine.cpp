@@ -96,7 +96,7 @@ void ccrdt_engine::release_all() {
                     &first_list, &ovl,
                     &hbm_scratch, &call_status, &val_cnt, &val_list, &val_keys, &val_ptr, &val_id,
                     &val_score, &cmp_cnt, &cmp_rows, &dwn_kind, &rpl_src, &rpl_key, &rpl_off, &lbr_lower,
-                    &lbr_base, &pt_cnt, &st_kp,
+                    &lbr_base, &pt_cnt, &grp_pair[0], &grp_pair[1], &grp_cnt, &grp_off, &st_kp,
                     &st_kind, &st_id, &st_score, &st_dc, &st_ts, &st_rvc, &st_out_kind, &st_out_vc})
     d->release();
   scan.release();

@@ -138,6 +138,9 @@ struct ccrdt_engine {
   // compaction's and the replication's scratch): the (part, key tile) counts
   // of ops and of clock rows
   ccrdt::DevBuf pt_cnt;
+  // group by key (group_kernels.hip): the two ping-pong sides of the (key, op
+  // index) pairs, the (digit, tile) counts and their exclusive scan
+  ccrdt::DevBuf grp_pair[2], grp_cnt, grp_off;
   int trmv_first_tier = 0;
   uint64_t last_n_ops = 0;
   uint64_t trmv_tot[2][3] = {};  // per side: bound on (players, pool, rows) held

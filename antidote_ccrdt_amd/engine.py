@@ -237,6 +237,65 @@ class DeviceSlice:
         self.base = self.p = None
 
 
+def _p(buf):
+    """A device pointer: of a buffer with `.p`, or the integer itself."""
+    return getattr(buf, "p", buf)
+
+
+def _group_columns(engine, n: int, d_key, cols: dict, alloc=None):
+    """An op stream resident in HBM in arrival order (COO: d_key = device
+    int64[n], cols = name -> (device buffer, element bytes 1 or 8)) grouped by
+    key on the device: engine.group_by_key_device, then every column moved
+    into that order by engine.gather_device.  Returns (key_ptr, src_op, name ->
+    grouped buffer), all new buffers from `alloc`; the inputs stay the
+    caller's.  The gathers are only enqueued on the engine stream."""
+    alloc = alloc or DeviceArray.empty
+    key_ptr, src_op = engine.group_by_key_device(d_key, n, alloc)
+    out, names = {}, list(cols)
+    try:
+        for c, (_, w) in cols.items():
+            out[c] = alloc(int(n) * w)
+        for at in range(0, len(names), _lib.GATHER_MAX_COLS):
+            engine.gather_device(n, src_op, [(cols[c][0], out[c], cols[c][1])
+                                             for c in names[at:at + _lib.GATHER_MAX_COLS]])
+    except BaseException:  # (a failed allocation or gather: nothing of the result is left to the collector)
+        for d in (key_ptr, src_op, *out.values()):
+            d.close()
+        raise
+    return key_ptr, src_op, out
+
+
+def _upload_coo(engine, key, cols: dict, build):
+    """Host columns in arrival order (each as long as `key`: ValueError
+    otherwise, since the gather checks an index against the op count, not
+    against a column's size) uploaded once, build(n, d_key, uploaded columns)
+    run over them, and the uploads released once the engine stream has
+    finished with them."""
+    key = _c(key, np.int64).reshape(-1)
+    n = int(key.shape[0])
+    for c, v in cols.items():
+        if v.ndim != 1 or v.shape[0] != n:
+            raise ValueError(f"column {c!r} has shape {v.shape}, the key column {n} ops")
+    made = []  # every upload so far: released whatever happens
+    try:
+        made.append(DeviceArray(key))
+        up = {}
+        for c, v in cols.items():
+            made.append(DeviceArray(v))
+            up[c] = made[-1]
+        res = build(n, made[0], up)
+        try:
+            engine.sync()
+        except BaseException:
+            for d in res:
+                d.close()
+            raise
+        return res
+    finally:
+        for d in made:
+            d.close()
+
+
 class _DeviceTrmvColumns:
     """Topk_rmv ops resident in HBM: one device buffer per name of COLUMNS,
     which are the pointer fields of the ctypes struct CSTRUCT, in its order."""
@@ -272,6 +331,40 @@ class DeviceTrmvBatch(_DeviceTrmvColumns):
         b = b.normalized()
         self._set(b.n_ops, int(b.rmv_vc.shape[0]), {f.name: DeviceArray(getattr(b, f.name)) for f in fields(b)},
                   int(np.count_nonzero(b.kind >= _lib.TRMV_RMV)))
+
+    OP_DTYPES = {"kind": np.uint8, "id": np.int64, "score": np.int64, "dc": np.uint8, "ts": np.int64}
+
+    @classmethod
+    def from_coo_buffers(cls, engine, n_ops: int, n_rmv: int, d_key, bufs: dict, n_rmv_ops: int | None = None):
+        """An effect batch from effects resident in HBM in arrival order:
+        d_key (device int64[n_ops]) is each effect's key, bufs maps kind, id,
+        score, dc, ts to its columns and rmv_vc to the n_rmv clock rows.  The
+        ops are grouped by key on the device (arrival order kept inside a
+        key); the clock rows are not moved -- a rmv keeps its ts, its row of
+        rmv_vc -- so the batch takes bufs["rmv_vc"] over as it is, while the
+        op columns stay the caller's.  Returns (batch, src_op): the batch
+        compact_device and apply_device take, and the device int64[n_ops] of
+        every grouped op's arrival position."""
+        cols = {c: (bufs[c], np.dtype(dt).itemsize) for c, dt in cls.OP_DTYPES.items()}
+        key_ptr, src_op, out = _group_columns(engine, n_ops, d_key, cols)
+        return cls.from_buffers(n_ops, n_rmv, {"key_ptr": key_ptr, **out, "rmv_vc": bufs["rmv_vc"]}, n_rmv_ops), src_op
+
+    @classmethod
+    def from_coo(cls, engine, key, kind, id, score, dc, ts, rmv_vc):
+        """from_coo_buffers for host columns in arrival order: one upload,
+        then grouped and gathered on the device."""
+        kind, rmv_vc = _c(kind, np.uint8), _c(rmv_vc, np.int64)
+        cols = {c: _c(v, cls.OP_DTYPES[c]) for c, v in zip(cls.OP_DTYPES, (kind, id, score, dc, ts))}
+        n_rmv_ops = int(np.count_nonzero(kind >= _lib.TRMV_RMV))
+
+        def build(n, d_key, up):
+            vc = DeviceArray(rmv_vc)  # the batch's own from here on; released here if the grouping fails
+            try:
+                return cls.from_coo_buffers(engine, n, int(rmv_vc.shape[0]), d_key, {**up, "rmv_vc": vc}, n_rmv_ops)
+            except BaseException:
+                vc.close()
+                raise
+        return _upload_coo(engine, key, cols, build)
 
     def to_host(self, n_dc: int) -> TrmvBatch:
         """The batch copied back to the host (n_ops ops, n_rmv clock rows of n_dc)."""
@@ -343,6 +436,28 @@ class DeviceRequests:
         d = cls.__new__(cls)
         d._set(n_req, bufs)
         return d
+
+    @classmethod
+    def from_coo_buffers(cls, engine, n_req: int, d_key, bufs: dict):
+        """Requests from a stream resident in HBM in arrival order: d_key
+        (device int64[n_req]) is each request's key, bufs maps op, id, score
+        (dc, ts: topk_rmv only) to its columns, which stay the caller's.  They
+        are grouped by key on the device, arrival order kept inside a key.
+        Returns (requests, src_op): what downstream_device takes, and the
+        device int64[n_req] of every grouped request's arrival position, by
+        which answers and op-indexed extras go back to the clients."""
+        width = {c: np.dtype(dt).itemsize for c, dt in zip(cls.COLUMNS, cls.DTYPES)}
+        key_ptr, src_op, out = _group_columns(engine, n_req, d_key, {c: (bufs[c], width[c]) for c in cls.COLUMNS[1:]
+                                                                     if c in bufs})
+        return cls.from_buffers(n_req, {"key_ptr": key_ptr, **out}), src_op
+
+    @classmethod
+    def from_coo(cls, engine, key, op, id, score, dc=None, ts=None):
+        """from_coo_buffers for host columns in arrival order: one upload,
+        then grouped and gathered on the device."""
+        cols = {c: _c(v, dt) for c, dt, v in zip(cls.COLUMNS[1:], cls.DTYPES[1:], (op, id, score, dc, ts))
+                if v is not None}
+        return _upload_coo(engine, key, cols, lambda n, d_key, up: cls.from_coo_buffers(engine, n, d_key, up))
 
     def close(self):
         for d in self.bufs.values():
@@ -418,6 +533,37 @@ class _Engine:
         device int64[n_ops] at d_key, entry i = the key whose range of the
         device uint64[n_keys + 1] at d_key_ptr holds i.  No wait."""
         check(lib.ccrdtx_csr_keys_device(self.h, d_key_ptr, int(n_ops), d_key), "csr_keys_device")
+
+    def group_by_key_device(self, d_key, n_ops: int, alloc=None):
+        """The inverse of csr_keys_device (ccrdtx_group_by_key_device): d_key
+        (a device buffer or pointer, int64[n_ops]) holds each op's key in
+        arrival order.  Returns (key_ptr, src_op): device uint64[n_keys + 1],
+        the CSR by key, and device int64[n_ops], the op indices grouped by
+        ascending key with arrival order kept inside a key, i.e.
+        np.argsort(key, kind="stable").  A key outside [0, n_keys) raises
+        CcrdtError(EINVAL).  The engine's state is not touched; one status
+        read-back is the call's wait.  `alloc` (bytes -> a buffer with `.p`
+        and `.close()`) provides the outputs."""
+        alloc = alloc or DeviceArray.empty
+        key_ptr, src_op = alloc(8 * (self.n_keys + 1)), alloc(8 * int(n_ops))
+        try:
+            check(lib.ccrdtx_group_by_key_device(self.h, int(n_ops), _p(d_key), key_ptr.p, src_op.p),
+                  "group_by_key_device")
+        except _lib.CcrdtError:
+            key_ptr.close()
+            src_op.close()
+            raise
+        return key_ptr, src_op
+
+    def gather_device(self, n_ops: int, src_op, cols) -> None:
+        """Enqueue out[o] = in[src_op[o]], o < n_ops, for 1 .. _lib.GATHER_MAX_COLS
+        columns at once (ccrdtx_gather_device): cols is a sequence of (in,
+        out, element bytes 1 or 8), in and out device buffers or pointers
+        that do not overlap; src_op device int64[n_ops].  An index outside
+        [0, n_ops) is skipped.  No wait."""
+        cols = list(cols)
+        cc = (_lib.Column * max(len(cols), 1))(*[_lib.Column(_p(i), _p(o), int(w)) for i, o, w in cols])
+        check(lib.ccrdtx_gather_device(self.h, int(n_ops), _p(src_op), len(cols), cc), "gather_device")
 
     def _values(self, name: str, keys):
         """ccrdt_<name>_value over `keys` (None: every key): (ptr uint64[n + 1],

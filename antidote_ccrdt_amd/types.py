@@ -517,6 +517,30 @@ class DeviceBatch:
         d.n, d.bufs = n, bufs
         return d
 
+    @classmethod
+    def from_coo_buffers(cls, engine, n: int, d_key, cols: dict):
+        """A batch from ops resident in HBM in arrival order: d_key (device
+        int64[n]) is each op's key, cols maps the batch's column names to
+        (device buffer, element bytes 1 or 8), which stay the caller's.  The
+        ops are grouped by key on the device (engine.group_by_key_device and
+        gather_device), arrival order kept inside a key.  Returns (batch with
+        key_ptr and the grouped columns, src_op = device int64[n] of every
+        grouped op's arrival position)."""
+        from .engine import _group_columns
+        key_ptr, src_op, out = _group_columns(engine, n, d_key, cols)
+        return cls.from_buffers(int(n), {"key_ptr": key_ptr, **out}), src_op
+
+    @classmethod
+    def from_coo(cls, engine, key, /, **arrays):
+        """from_coo_buffers for host columns in arrival order (elements of 1
+        or 8 bytes): one upload, then grouped and gathered on the device.  For
+        a leaderboard: from_coo(engine, key, kind=uint8, id=int64,
+        score=int64) is what LeaderboardEngine.apply_device takes."""
+        from .engine import _upload_coo
+        cols = {c: np.ascontiguousarray(v) for c, v in arrays.items()}
+        return _upload_coo(engine, key, cols, lambda n, d_key, up: cls.from_coo_buffers(
+            engine, n, d_key, {c: (up[c], cols[c].dtype.itemsize) for c in cols}))
+
     def __getitem__(self, k):
         return self.bufs[k].p
 

@@ -168,6 +168,52 @@ int ccrdtx_trmv_partition_device(ccrdt_engine* e, int64_t n_src_keys, const ccrd
                                  const ccrdtx_trmv_parts* dev_out, int64_t cap_ops, int64_t cap_rows,
                                  int64_t* part_ops, int64_t* part_rows, int64_t* part_keys_base);
 
+/* Ops of one workgroup tile of the group-by-key passes (8 rounds of 256
+ * threads); key bits one pass sorts by; columns per gather call. */
+#define CCRDTX_GROUP_TILE 2048
+#define CCRDTX_GROUP_BITS 8
+#define CCRDTX_GATHER_MAX_COLS 8
+/* The inverse of ccrdtx_csr_keys_device: an op stream resident in HBM in
+ * arrival order, each op with its key (COO), grouped by key.  d_key (device,
+ * int64[n_ops]): d_key[i] is the key of op i.  d_src_op (device,
+ * int64[n_ops]): the op indices by ascending key, arrival order kept inside a
+ * key -- np.argsort(key, kind="stable"); output op o is input op d_src_op[o].
+ * d_key_ptr (device, uint64[n_keys + 1]): the CSR over that order, n_keys the
+ * engine's.  An engine of any type; its resident state is neither read nor
+ * changed, it lends its stream and scratch (two buffers of 8 * n_ops bytes for
+ * the (key, op index) pairs and 12 bytes per 8 ops for the tile counts).  A
+ * least-significant-digit radix sort over the key's bits above, 8 per pass:
+ * 1 pass up to 256 keys, 2 up to 65,536, 3 up to 2^24, 4 at most.  The work
+ * is enqueued on the engine stream; the call then reads back one status
+ * record, its only wait.  CCRDT_EINVAL, with nothing written to d_key_ptr or
+ * d_src_op: a key outside [0, n_keys), n_ops < 0 or n_ops >= 2^32, an engine
+ * of more than 2^32 keys, a null d_key_ptr, a null d_key or d_src_op with
+ * n_ops > 0, a null engine (nothing is touched).  After any error the engine
+ * stays usable.  n_ops == 0 is valid (d_key and d_src_op may then be NULL):
+ * all of d_key_ptr is 0. */
+int ccrdtx_group_by_key_device(ccrdt_engine* e, int64_t n_ops, const int64_t* d_key, uint64_t* d_key_ptr,
+                               int64_t* d_src_op);
+
+/* One column of ccrdtx_gather_device: `in` and `out` are device memory of
+ * n_ops elements of `width` bytes (1 or 8) each and must not overlap. */
+typedef struct {
+  const void* in;
+  void* out;
+  int32_t width;
+} ccrdtx_column;
+/* The columns of an op stream moved into a grouped order: for each of the
+ * n_cols columns (1 .. CCRDTX_GATHER_MAX_COLS; cols is a host array)
+ * out[o] = in[d_src_op[o]] for o in [0, n_ops).  d_src_op (device,
+ * int64[n_ops]) is read once for all columns.  An index outside [0, n_ops) is
+ * skipped: nothing is read for it and that element of every `out` is left as
+ * it was.  An engine of any type lends its stream; the call is only enqueued
+ * and does not wait.  CCRDT_EINVAL, with nothing enqueued: a width other than
+ * 1 or 8, n_cols out of range, n_ops < 0 or n_ops >= 2^32, null cols, a null
+ * d_src_op, `in` or `out` with n_ops > 0, a null engine.  n_ops == 0 is valid
+ * and does nothing. */
+int ccrdtx_gather_device(ccrdt_engine* e, int64_t n_ops, const int64_t* d_src_op, int n_cols,
+                         const ccrdtx_column* cols);
+
 #ifdef __cplusplus
 }
 #endif
