@@ -272,6 +272,11 @@ EXT_SIGNATURES = {
                                            P, P, P]),
     "ccrdtx_group_by_key_device": (INT, [P, I64, P, P, P]),
     "ccrdtx_gather_device": (INT, [P, I64, P, INT, C.POINTER(Column)]),
+    "ccrdtx_topk_value_size": (INT, [P, I64, P, C.POINTER(I64)]),
+    "ccrdtx_topk_value": (INT, [P, I64, P, P, P, P]),
+    "ccrdtx_topk_value_device": (INT, [P, I64, P, P, P, P, I64]),
+    "ccrdtx_avg_value": (INT, [P, I64, P, P, P]),
+    "ccrdtx_avg_value_device": (INT, [P, I64, P, P, P]),
 }
 
 

@@ -118,7 +118,8 @@ struct ccrdt_engine {
   ccrdt::DevBuf call_status;
   // batched value/1 (value_kernels.hip): per listed key its |Observed|, the
   // handed-on list (count first), and the host variant's uploaded keys and
-  // device-side result
+  // device-side result.  The keyed value/1 of topk and average
+  // (topk_value_kernels.hip) uses the same scratch: an engine has one type.
   ccrdt::DevBuf val_cnt, val_list, val_keys, val_ptr, val_id, val_score;
   // device log compaction (compact_kernels.hip; both types it serves): per-key
   // kept counts, each key's first clock row

@@ -565,22 +565,26 @@ class _Engine:
         cc = (_lib.Column * max(len(cols), 1))(*[_lib.Column(_p(i), _p(o), int(w)) for i, o, w in cols])
         check(lib.ccrdtx_gather_device(self.h, int(n_ops), _p(src_op), len(cols), cc), "gather_device")
 
-    def _values(self, name: str, keys):
-        """ccrdt_<name>_value over `keys` (None: every key): (ptr uint64[n + 1],
-        id int64, score int64), each key's pairs ranked by cmp/2."""
+    def _key_list(self, keys):
+        """(n, keys uint64[n] or None) of a value/1 key list (None: every key)."""
         if keys is None:
-            n, kp = self.n_keys, None
-        else:
-            keys = np.asarray(keys)
-            if keys.dtype != np.uint64:  # (a negative index wraps and is refused as out of range)
-                keys = keys.astype(np.int64).astype(np.uint64)
-            keys = _c(keys, np.uint64).reshape(-1)
-            n, kp = int(keys.shape[0]), ptr(keys)
+            return self.n_keys, None
+        keys = np.asarray(keys)
+        if keys.dtype != np.uint64:  # (a negative index wraps and is refused as out of range)
+            keys = keys.astype(np.int64).astype(np.uint64)
+        keys = _c(keys, np.uint64).reshape(-1)
+        return int(keys.shape[0]), keys
+
+    def _values(self, name: str, keys, prefix: str = "ccrdt_"):
+        """<prefix><name>_value over `keys` (None: every key): (ptr uint64[n + 1],
+        id int64, score int64), each key's pairs ranked by cmp/2."""
+        n, keys = self._key_list(keys)
+        kp = ptr(keys)
         tot = C.c_int64()
-        check(getattr(lib, f"ccrdt_{name}_value_size")(self.h, n, kp, C.byref(tot)), f"{name}_value_size")
+        check(getattr(lib, f"{prefix}{name}_value_size")(self.h, n, kp, C.byref(tot)), f"{name}_value_size")
         p = np.zeros(n + 1, np.uint64)
         i, s = np.zeros(max(tot.value, 1), np.int64), np.zeros(max(tot.value, 1), np.int64)
-        check(getattr(lib, f"ccrdt_{name}_value")(self.h, n, kp, ptr(p), ptr(i), ptr(s)), f"{name}_value")
+        check(getattr(lib, f"{prefix}{name}_value")(self.h, n, kp, ptr(p), ptr(i), ptr(s)), f"{name}_value")
         return p, i[:tot.value], s[:tot.value]
 
     def close(self):

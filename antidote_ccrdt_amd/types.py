@@ -58,6 +58,21 @@ class AverageEngine(_Engine):
         check(lib.ccrdt_avg_value(self.h, ptr(v), ptr(d)), "avg_value")
         return v, d.astype(bool)
 
+    def values(self, keys=None):
+        """value/1 (average.erl:68-70) of `keys` (key indices in any order,
+        repeats allowed; None: every key) read on the device: (value float64[n],
+        defined bool[n]); only the listed keys cross to the host."""
+        n, keys = self._key_list(keys)
+        v, d = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint8)
+        check(lib.ccrdtx_avg_value(self.h, n, ptr(keys), ptr(v), ptr(d)), "avg_value")
+        return v[:n], d[:n].astype(bool)
+
+    def values_device(self, n: int, d_keys: int | None, d_value: int, d_defined: int) -> None:
+        """Enqueue values() of n keys (device uint64[n] at d_keys, None: key i
+        = i) into device float64[n] / uint8[n]; an out-of-range key gives
+        defined = 0, value = 0.0.  No wait."""
+        check(lib.ccrdtx_avg_value_device(self.h, n, d_keys, d_value, d_defined), "avg_values_device")
+
 
 # --------------------------------------------------------------------- topk
 class TopkEngine(_Engine):
@@ -94,6 +109,22 @@ class TopkEngine(_Engine):
     def value(self):
         """value/1 of every key: Score desc, Id desc (GPU segmented sort)."""
         return self._out(lib.ccrdt_topk_value, "topk_value")
+
+    def values(self, keys=None):
+        """value/1 (topk.erl:81-83) of `keys` (key indices in any order, repeats
+        allowed; None: every key) read and ordered on the device: (ptr, id,
+        score), segment i = the whole map of keys[i] as {Id, Score}, Score
+        descending, then Id descending.  Only the listed keys' state is read
+        and only their entries cross to the host."""
+        return self._values("topk", keys, prefix="ccrdtx_")
+
+    def values_device(self, n: int, d_keys: int | None, d_ptr: int, d_id: int, d_score: int,
+                      cap_entries: int) -> None:
+        """Enqueue values() of n keys (device uint64[n] at d_keys, None: key i
+        = i) into device arrays: d_ptr uint64[n + 1] always complete, d_id /
+        d_score int64[cap_entries] written for every key that fits whole.  No
+        wait."""
+        check(lib.ccrdtx_topk_value_device(self.h, n, d_keys, d_ptr, d_id, d_score, cap_entries), "topk_values_device")
 
     def import_state(self, p, i, s) -> None:
         p, i, s = _c(p, np.uint64), _c(i, np.int64), _c(s, np.int64)

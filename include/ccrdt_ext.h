@@ -214,6 +214,42 @@ typedef struct {
 int ccrdtx_gather_device(ccrdt_engine* e, int64_t n_ops, const int64_t* d_src_op, int n_cols,
                          const ccrdtx_column* cols);
 
+/* Keyed, batched value/1 of topk (topk.erl:81-83) read and ordered on the
+ * device, under the contract of ccrdt_trmv_value* (ccrdt.h).  keys: n key
+ * indices in any order, repeats allowed, each occurrence with a segment of its
+ * own; NULL means key i = i, with n <= n_keys.  Segment i, entries [ptr[i],
+ * ptr[i+1]) of id / score, is the whole map of keys[i] as {Id, Score} -- value/1
+ * of topk is not truncated to Size -- ordered Score descending, then Id
+ * descending.  A fresh or reset engine gives all-empty segments.  Only the
+ * listed keys' state is read, and only their entries cross to the host.
+ * _value_size: *n_entries = the entries ccrdtx_topk_value writes for the same
+ * list.  ptr has n + 1 entries, id and score that total.  CCRDT_EINVAL, with
+ * nothing written: a key outside [0, n_keys), n < 0 or n >= 2^32 - 1, n >
+ * n_keys without a list, a NULL output, a null engine ("null engine", before
+ * any output is touched).  CCRDT_ENOSYS: an engine of another type.  n == 0 is
+ * valid: ptr[0] = 0. */
+int ccrdtx_topk_value_size(ccrdt_engine* e, int64_t n, const uint64_t* keys, int64_t* n_entries);
+int ccrdtx_topk_value(ccrdt_engine* e, int64_t n, const uint64_t* keys, uint64_t* ptr, int64_t* id, int64_t* score);
+/* The same into device memory (d_keys, d_ptr, d_id, d_score), only enqueued on
+ * the engine stream: the call never waits, and it reads the state as it is in
+ * stream order.  d_ptr[0 .. n] is always written in full and d_ptr[n] is the
+ * true total.  A key's entries are written only if the whole key fits
+ * (d_ptr[i+1] <= cap_entries); nothing at or past cap_entries is touched.  A
+ * key outside [0, n_keys) in a device list yields an empty segment and reads
+ * nothing.  A key of more than 4096 entries is sorted in place in its own
+ * segment of d_id / d_score, so the call needs no scratch sized by the result. */
+int ccrdtx_topk_value_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys, uint64_t* d_ptr, int64_t* d_id,
+                             int64_t* d_score, int64_t cap_entries);
+
+/* Keyed value/1 of average (average.erl:68-70) for a key list as above:
+ * value[i] = Sum / Num of keys[i] as IEEE doubles and defined[i] = (Num != 0),
+ * value[i] = 0.0 where it is not; what ccrdt_avg_value gives for that key.
+ * Errors as for ccrdtx_topk_value.  The _device form is only enqueued on the
+ * engine stream; a key outside [0, n_keys) in a device list gives defined = 0,
+ * value = 0.0. */
+int ccrdtx_avg_value(ccrdt_engine* e, int64_t n, const uint64_t* keys, double* value, uint8_t* defined);
+int ccrdtx_avg_value_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys, double* d_value, uint8_t* d_defined);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,10 @@ also reports its algorithmic bytes -- per listed key 32 (meta) + 4 np (player
 statuses) + nobs (8 Id + 4 slab + 8 Score) read, 16 nobs + 8 written -- and
 the fraction of the 8 TB/s HBM peak they make of the measured time.
 
-    python tools/value_bench.py [--types trmv,lb] [--n-ops N --n-keys N] [--lb-ops N]
+--types topk adds the topk leg (bench_topk): the keyed read of 1, 1,000 and
+all keys against the whole-engine ccrdt_topk_value on the same state.
+
+    python tools/value_bench.py [--types trmv,lb,topk] [--n-ops N --n-keys N] [--lb-ops N] [--topk-ops N --topk-keys N]
                                 [--export-runs R] [--package-root DIR] [--label L] [--out FILE]
 """
 import argparse
@@ -131,9 +134,66 @@ def bench_lb(args):
     return out
 
 
+def bench_topk(args):
+    """The topk leg (--types topk): the keyed read of 1, 1,000 and all keys,
+    device variant (HIP events, 5 warm-ups + 20 runs) and host variant (wall),
+    and the whole-engine ccrdt_topk_value on the same state, the two host
+    reads of all keys alternating.  State: bench_types.py's topk after one
+    batch (id U[0,1000), score U[1,1e6], ops spread uniformly over the keys)."""
+    from antidote_ccrdt_amd.engine import DeviceArray
+    from antidote_ccrdt_amd.types import DeviceBatch, TopkEngine
+    rng = np.random.default_rng(0xCC0DE)
+    n, nk = args.topk_ops, args.topk_keys
+    kp = np.zeros(nk + 1, np.uint64)
+    np.cumsum(rng.multinomial(n, np.full(nk, 1.0 / nk)), out=kp[1:])
+    d = DeviceBatch(n, key_ptr=kp, id=rng.integers(0, 1000, n, dtype=np.int64),
+                    score=rng.integers(1, 10**6 + 1, n, dtype=np.int64))
+    eng = TopkEngine(nk, args.k)
+    eng.apply_device(d)
+    eng.sync()
+    d.close()
+    out = {"type": "topk", "n_ops": n, "n_keys": nk, "entries": eng.size()}
+    if not hasattr(eng, "values_device"):
+        out["value_all_ms"] = stats(wall(eng.value, 5))
+        eng.close()
+        return out
+    whole, keyed = eng.value(), eng.values()
+    out["same_result"] = all(np.array_equal(x, y) for x, y in zip(whole, keyed))
+    sizes = np.diff(whole[0].astype(np.int64))
+    out["entries_per_key"] = {"min": int(sizes.min()), "median": float(np.median(sizes)), "max": int(sizes.max())}
+    del whole, keyed
+    t_whole, t_keyed = [], []
+    for _ in range(5):  # alternating: the same host, the same minute
+        t_whole += wall(eng.value, 1)
+        t_keyed += wall(eng.values, 1)
+    out["value_all_ms"], out["values_all_ms"] = stats(t_whole), stats(t_keyed)
+    for name, keys in (("1", np.array([nk // 2], np.uint64)),
+                       ("1000", rng.choice(nk, min(1000, nk), replace=False).astype(np.uint64)), ("all", None)):
+        m = nk if keys is None else int(keys.shape[0])
+        if keys is not None:
+            out[f"values_{name}_ms"] = stats(wall(lambda: eng.values(keys), 200))
+        total = int(eng.values(keys)[0][-1])
+        dk = DeviceArray(keys) if keys is not None else None
+        bufs = [DeviceArray.empty(8 * (m + 1)), DeviceArray.empty(8 * max(total, 1)), DeviceArray.empty(8 * max(total, 1))]
+        ms = []
+        for i in range(25):
+            eng.timer_start()
+            eng.values_device(m, dk.p if dk else None, *(b.p for b in bufs), total)
+            t = eng.timer_stop()
+            if i >= 5:
+                ms.append(t)
+        for b in bufs + ([dk] if dk else []):
+            b.close()
+        out[f"value_device_{name}_ms"] = dict(stats(ms), entries=total)
+    eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--types", default="trmv,lb")
+    ap.add_argument("--types", default="trmv,lb", help="trmv, lb, topk (comma-separated)")
+    ap.add_argument("--topk-ops", type=int, default=100_000_000)
+    ap.add_argument("--topk-keys", type=int, default=1 << 20)
     ap.add_argument("--n-ops", type=int, default=100_000_000)
     ap.add_argument("--n-keys", type=int, default=1 << 20)
     ap.add_argument("--k", type=int, default=100)
@@ -151,7 +211,7 @@ def main():
     if _lib.device_count() < 1:
         raise SystemExit("value_bench: no HIP device visible (there is no CPU path to time)")
     for t in args.types.split(","):
-        r = {"trmv": bench_trmv, "lb": bench_lb}[t](args)
+        r = {"trmv": bench_trmv, "lb": bench_lb, "topk": bench_topk}[t](args)
         r["label"] = args.label
         line = json.dumps(r)
         print(line, flush=True)
