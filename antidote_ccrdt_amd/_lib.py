@@ -277,6 +277,11 @@ EXT_SIGNATURES = {
     "ccrdtx_topk_value_device": (INT, [P, I64, P, P, P, P, I64]),
     "ccrdtx_avg_value": (INT, [P, I64, P, P, P]),
     "ccrdtx_avg_value_device": (INT, [P, I64, P, P, P]),
+    # ccrdtx_lb_image has the layout of ccrdt_lb_state
+    "ccrdtx_lb_export_keys_device": (INT, [P, I64, P, C.POINTER(LbState), I64, I64, I64, C.POINTER(I64)]),
+    "ccrdtx_lb_import_keys_device": (INT, [P, I64, P, C.POINTER(LbState)]),
+    "ccrdtx_lb_export_keys": (INT, [P, I64, P, C.POINTER(LbState), I64, I64, I64, C.POINTER(I64)]),
+    "ccrdtx_lb_import_keys": (INT, [P, I64, P, C.POINTER(LbState)]),
 }
 
 

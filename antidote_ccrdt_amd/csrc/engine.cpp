@@ -101,6 +101,7 @@ void ccrdt_engine::release_all() {
     d->release();
   scan.release();
   wcv.release();
+  lbs.release();
   release_types();
 }
 

@@ -62,6 +62,18 @@ struct WcValBufs {
   }
 };
 
+// Scratch of the keyed state images of the leaderboard (lb_state_kernels.hip),
+// grown on demand.
+struct LbStateBufs {
+  DevBuf cnt, ptr, list;          // export: per position the three list sizes, their scans, the handed-on list
+  DevBuf slot, minq, newn, off;   // import: key -> position + 1, each position's minq, new board sizes and starts
+  DevBuf keys, img[11];           // the host forms' uploaded key list and device-side image
+  void release() {
+    for (DevBuf* d : {&cnt, &ptr, &list, &slot, &minq, &newn, &off, &keys}) d->release();
+    for (DevBuf& d : img) d.release();
+  }
+};
+
 }  // namespace ccrdt
 
 struct ccrdt_engine {
@@ -160,6 +172,7 @@ struct ccrdt_engine {
   // other types
   ccrdt::TypeBufs tb;
   ccrdt::WcValBufs wcv;
+  ccrdt::LbStateBufs lbs;
 
   ccrdt::TrmvSide trmv_side(int ms, int ds) const;
   ccrdt::TrmvSide trmv_cur() const { return trmv_side(mcur, cur); }

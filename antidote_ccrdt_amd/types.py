@@ -217,6 +217,49 @@ class DeviceLbRun:
             d.close()
 
 
+class DeviceLbImage:
+    """The canonical image of n leaderboard boards resident in HBM
+    (ccrdtx_lb_image: the layout of LbState for n boards, back to back): what
+    LeaderboardEngine.export_keys_device leaves and import_keys_device takes.
+    `caps` = the (Observed, Masked, Bans) entries its lists have room for,
+    `totals` = the entries they hold."""
+    FIELDS = tuple((f.name, np.uint8 if f.name == "min_valid" else np.uint64 if f.name.endswith("ptr") else np.int64)
+                   for f in fields(LbState))
+
+    def __init__(self, n: int, caps, alloc=None):
+        from .engine import DeviceArray
+        self.n, self.caps, self.totals = int(n), tuple(int(c) for c in caps), (0, 0, 0)
+        self.bufs = {f: (alloc or DeviceArray.empty)(self._count(f) * np.dtype(t).itemsize) for f, t in self.FIELDS}
+        self.c = _lib.LbState(*[self.bufs[f].p for f, _ in self.FIELDS])
+
+    def _count(self, f: str, held: bool = False) -> int:
+        if f.endswith("ptr"):
+            return self.n + 1
+        if f.startswith("min"):
+            return self.n
+        return (self.totals if held else self.caps)["omb".index(f[0])]
+
+    @classmethod
+    def from_host(cls, st: LbState) -> "DeviceLbImage":
+        """The image `st` (an LbState of any number of boards) uploaded."""
+        n = int(st.obs_ptr.shape[0]) - 1
+        d = cls(n, (int(st.obs_ptr[n]), int(st.m_ptr[n]), int(st.b_ptr[n])))
+        d.totals = d.caps
+        for f, t in cls.FIELDS:
+            a = _c(getattr(st, f), t)
+            if a.nbytes:
+                check(lib.ccrdt_memcpy_h2d(d.bufs[f].p, ptr(a), a.nbytes), "h2d")
+        return d
+
+    def to_host(self) -> LbState:
+        """The image copied back to the host, its lists cut to `totals`."""
+        return LbState(*[self.bufs[f].to_host(t, self._count(f, held=True)) for f, t in self.FIELDS])
+
+    def close(self):
+        for d in self.bufs.values():
+            d.close()
+
+
 class LeaderboardEngine(_Engine):
     """antidote_ccrdt_leaderboard (src/antidote_ccrdt_leaderboard.erl)."""
     TYPE = _lib.LEADERBOARD
@@ -384,6 +427,75 @@ class LeaderboardEngine(_Engine):
     def import_range(self, k0: int, k1: int, st: LbState) -> None:
         cs = st.as_c()
         check(lib.ccrdt_lb_import_range(self.h, k0, k1, C.byref(cs)), "lb_import_range")
+
+    def _export_keys(self, fn, where: str, n: int, keys, image, caps):
+        """One ccrdtx_lb_export_keys* call: the (Observed, Masked, Bans) totals;
+        a total over its capacity raises CcrdtError(ENOMEM) carrying them."""
+        tot = (C.c_int64 * 3)()
+        try:
+            check(fn(self.h, n, keys, C.byref(image), *caps, tot), where)
+        except _lib.CcrdtError as err:
+            err.totals = tuple(int(t) for t in tot)
+            raise
+        return tuple(int(t) for t in tot)
+
+    def _export_sizes(self, fn, where: str, n: int, keys, image):
+        """The sizing call (capacities 0): the totals."""
+        try:
+            return self._export_keys(fn, where, n, keys, image, (0, 0, 0))
+        except _lib.CcrdtError as err:
+            if err.code != _lib.ENOMEM:
+                raise
+            return err.totals
+
+    def export_keys(self, keys=None) -> LbState:
+        """The image of boards `keys` (board indices in any order, repeats
+        allowed; None: every board), built on the device
+        (ccrdtx_lb_export_keys): segment i is what export_range(k, k + 1) gives
+        for k = keys[i].  Only the listed boards cross to the host."""
+        n, keys = self._key_list(keys)
+        st = self._empty(n, 0, 0, 0)
+        tot = self._export_sizes(lib.ccrdtx_lb_export_keys, "lb_export_keys", n, ptr(keys), st.as_c())
+        if any(tot):
+            st = self._empty(n, *tot)
+            self._export_keys(lib.ccrdtx_lb_export_keys, "lb_export_keys", n, ptr(keys), st.as_c(), tot)
+        return st
+
+    def import_keys(self, keys, st: LbState) -> None:
+        """Board keys[i] := segment i of the image `st` (ccrdtx_lb_import_keys;
+        None: board i = segment i); every other board keeps its state and only
+        the listed boards cross to the device.  An invalid image raises
+        CcrdtError(EINVAL) and leaves the state as it was."""
+        n, keys = self._key_list(keys) if keys is not None else (int(st.obs_ptr.shape[0]) - 1, None)
+        host = LbState(*[_c(getattr(st, f), t) for f, t in DeviceLbImage.FIELDS])  # (kept alive over the call)
+        cs = host.as_c()
+        check(lib.ccrdtx_lb_import_keys(self.h, n, ptr(keys), C.byref(cs)), "lb_import_keys")
+
+    def export_keys_device(self, d_keys: int | None, n: int, caps=None, alloc=None) -> DeviceLbImage:
+        """export_keys of n boards (device uint64[n] at d_keys, None: board i)
+        into a DeviceLbImage, against the state as it is in stream order
+        (ccrdtx_lb_export_keys_device).  caps: the (Observed, Masked, Bans)
+        capacities of its lists; None: a sizing call first.  A total over its
+        capacity raises CcrdtError(ENOMEM) with `totals`."""
+        if caps is None:
+            probe = DeviceLbImage(n, (0, 0, 0), alloc)
+            try:
+                caps = self._export_sizes(lib.ccrdtx_lb_export_keys_device, "lb_export_keys_device", n, d_keys, probe.c)
+            finally:
+                probe.close()
+        img = DeviceLbImage(n, caps, alloc)
+        try:
+            img.totals = self._export_keys(lib.ccrdtx_lb_export_keys_device, "lb_export_keys_device", n, d_keys,
+                                           img.c, img.caps)
+        except _lib.CcrdtError:
+            img.close()
+            raise
+        return img
+
+    def import_keys_device(self, d_keys: int | None, n: int, image: DeviceLbImage) -> None:
+        """import_keys of n boards from an image resident in HBM
+        (ccrdtx_lb_import_keys_device)."""
+        check(lib.ccrdtx_lb_import_keys_device(self.h, n, d_keys, C.byref(image.c)), "lb_import_keys_device")
 
     def downstream(self, key, op, id, score):
         key = _c(key, np.uint64)

@@ -250,6 +250,72 @@ int ccrdtx_topk_value_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys,
 int ccrdtx_avg_value(ccrdt_engine* e, int64_t n, const uint64_t* keys, double* value, uint8_t* defined);
 int ccrdtx_avg_value_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys, double* d_value, uint8_t* d_defined);
 
+/* The canonical image of n listed leaderboard boards: the layout of
+ * ccrdt_lb_state (ccrdt.h) for n boards, back to back in list order. */
+typedef struct {
+  uint64_t* obs_ptr; /* [n + 1] */
+  int64_t *obs_id, *obs_score; /* [cap_obs] */
+  uint64_t* m_ptr;   /* [n + 1] */
+  int64_t *m_id, *m_score;     /* [cap_masked] */
+  uint64_t* b_ptr;   /* [n + 1] */
+  int64_t* b_id;     /* [cap_bans] */
+  uint8_t* min_valid;          /* [n] */
+  int64_t *min_id, *min_score; /* [n] */
+} ccrdtx_lb_image;
+/* Size classes of the export by a board's entry count (Observed + Masked +
+ * Bans): a wave ranks up to CCRDTX_LB_STATE_WAVE_MAX entries by counting, a
+ * workgroup sorts up to CCRDTX_LB_STATE_LDS_MAX in LDS, a larger board is
+ * sorted in place in its own output segments. */
+#define CCRDTX_LB_STATE_WAVE_MAX 128
+#define CCRDTX_LB_STATE_LDS_MAX 4096
+/* The image of the listed boards, built on the device into device arrays
+ * (d_keys and every array of dev_out are device memory; dev_out itself and
+ * totals are host memory).  d_keys: n board indices in any order, repeats
+ * allowed, each occurrence with segments of its own; NULL means key i = i,
+ * with n <= n_keys.  Segment i of each list is what ccrdt_lb_export_range(e,
+ * k, k + 1) gives for k = d_keys[i]: Observed, Masked and Bans each ascending
+ * by Id, and Min (0 / 0 / 0 when nil).  The work is enqueued on the engine
+ * stream and reads the state as it is in stream order; the call then reads
+ * back one status record, its only wait.  totals = the {Observed, Masked,
+ * Bans} entries of the list, always the true ones.  CCRDT_ENOMEM: a total
+ * exceeds its capacity; the three ptr arrays and the Min columns are still
+ * written in full, a board's lists are written only if the whole board lies
+ * below all three capacities, and nothing at or past a capacity is touched
+ * (capacities 0: the sizing call; the id / score arrays may then be NULL).
+ * CCRDT_EINVAL, with nothing written: a key outside [0, n_keys), n < 0 or n >=
+ * 2^32 - 1, n > n_keys without a list, a negative capacity, a null output
+ * array, a null engine ("null engine", before anything is touched).
+ * CCRDT_ENOSYS: an engine of another type.  A fresh or reset engine gives
+ * empty boards.  The resident state is never changed. */
+int ccrdtx_lb_export_keys_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys, const ccrdtx_lb_image* dev_out,
+                                 int64_t cap_obs, int64_t cap_masked, int64_t cap_bans, int64_t totals[3]);
+/* Board d_keys[i] of the engine becomes exactly segment i of the image (all
+ * device memory; d_keys NULL: key i = i); every other board keeps its state.
+ * The new state is built on the device into the engine's other state buffer;
+ * the call reads back one status record and only on success makes that buffer
+ * the current one, so any error leaves the state untouched and the engine
+ * usable.  Every unlisted board is copied into that buffer, so the call
+ * costs O(resident state) of device bandwidth whatever the list holds, and
+ * the build pass is still on the engine stream when it returns.  The last
+ * apply's extras stay as ccrdt_lb_import leaves them.
+ * CCRDT_EINVAL, decided on the device: a key outside [0, n_keys) or listed
+ * twice; a ptr array not monotone from 0; a list not strictly ascending by Id;
+ * an Id in two lists of one board; |Observed| > Size; Masked non-empty with
+ * |Observed| != Size; min_valid with (min_id, min_score) not an Observed pair;
+ * !min_valid with Observed non-empty.  Also n < 0, n >= 2^32 - 1, n > n_keys
+ * without a list, a null array, a null engine.  CCRDT_ENOMEM: the new entry
+ * total reaches 2^32 - 1.  CCRDT_ENOSYS: an engine of another type.  n == 0 is
+ * valid and changes nothing. */
+int ccrdtx_lb_import_keys_device(ccrdt_engine* e, int64_t n, const uint64_t* d_keys, const ccrdtx_lb_image* dev_in);
+/* The same over host memory (keys and every array of the image): the key list
+ * (and, for the import, the image) is uploaded, the device form runs, and the
+ * export downloads what it wrote -- with CCRDT_ENOMEM the ptr arrays, the Min
+ * columns and the boards that fit.  Only the listed boards cross to or from
+ * the host. */
+int ccrdtx_lb_export_keys(ccrdt_engine* e, int64_t n, const uint64_t* keys, const ccrdtx_lb_image* out,
+                          int64_t cap_obs, int64_t cap_masked, int64_t cap_bans, int64_t totals[3]);
+int ccrdtx_lb_import_keys(ccrdt_engine* e, int64_t n, const uint64_t* keys, const ccrdtx_lb_image* in);
+
 #ifdef __cplusplus
 }
 #endif
